@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """Training-step throughput of the HD-GNN/S engine on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the result line (metric, value, ms_per_step, config).
+--full adds every side measurement to that line: the re-timed upload + prepare, the
+steady-state re-timing, the per-kernel HIP-event pass and its roofline, the data-parallel
+tail time, the reference training loop (--e2e) and the CPU baseline (--no-cpu skips it).
 
 `--gpus N` without a launcher starts the N ranks itself (a torch.distributed.run child);
 under a launcher WORLD_SIZE must equal --gpus.  Rank r runs on device r mod device_count;
@@ -12,8 +18,8 @@ A step = the fused step kernel + the gradient reduction + TF Adam on 100 residen
 synthetic glide-shaped commits per GPU (weak scaling); under torch.distributed.run the
 reduction kernel also all-reduces the flat gradient over xGMI (hdg_train_step_dp; RCCL
 when HDG_DP_ALLREDUCE=rccl or the ranks span hosts).  Rank 0 prints
-one JSON line.  Per-kernel durations come from HIP events recorded on the launch stream;
-the CPU baseline is oracle/literal.py (the TF graph's op sequence on torch-CPU).
+one JSON line.  With --full, per-kernel durations come from HIP events recorded on the
+launch stream; the CPU baseline is oracle/literal.py (the TF graph's op sequence on torch-CPU).
 """
 import argparse
 import json
@@ -235,6 +241,75 @@ def e2e_train(B, ne, nc, v, epochs, dev):
                     "and a TF-bundle checkpoint written by libhdgnn on the saver thread"}
 
 
+DUMP_BUDGET = 48 << 20      # bytes of --dump-outputs arrays over all ranks (limit: 64 MB)
+
+
+def _sample(a, max_elems, seed=20250301):
+    """`a` itself when it fits, else a fixed seeded sample of its flattened elements (the
+    same positions in every run of the same shape)."""
+    if a.size <= max_elems:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, max_elems, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def fetch_outputs(eng):
+    """What a caller of the timed path (Engine.train_step / replay) holds after a step: the
+    pair probabilities and the stats row of that step, and the updated parameters."""
+    return {"probs": eng.probs.cpu().numpy(), "stats": eng.stats.cpu().numpy(),
+            "params": eng.get_params()}
+
+
+def dump_outputs(d, outs, rank, world):
+    """DIR/<name>.npy in float32 (rank 0; rank r > 0 of a data-parallel run writes
+    <name>.rank<r>.npy), probs sampled down when all ranks' would pass DUMP_BUDGET."""
+    os.makedirs(d, exist_ok=True)
+    small = sum(a.nbytes for k, a in outs.items() if k != "probs")
+    outs = dict(outs, probs=_sample(outs["probs"], (DUMP_BUDGET // world - small) // 4))
+    for k, a in outs.items():
+        name = k if rank == 0 else "%s.rank%d" % (k, rank)
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
+def kernel_events(eng, db, nev, dev):
+    """(per-kernel ms, data-parallel tail ms) averaged over `nev` instrumented steps."""
+    # per-kernel durations: HIP events on the launch stream after every kernel launch of
+    # the step (hdg_fwd_bwd_kernel_events), eager launches, a separate instrumented pass
+    # with the training step's outputs (probs, as the training sess.run fetches; no logits)
+    import ctypes
+    from hdgnn import _lib
+    NEV = 40
+    ev = _lib.HipEvents(NEV)
+    kn = (ctypes.c_char_p * (NEV - 1))()
+    nk = ctypes.c_int32()
+    acc, order = {}, []
+    tails = []                  # data parallel: the all-reduce + Adam tail after fwd_bwd
+    for _ in range(nev):
+        bstruct = db.struct()
+        _lib.check(eng.lib.hdg_fwd_bwd_kernel_events(
+            ctypes.byref(eng.shape), ctypes.byref(bstruct), ctypes.c_void_p(eng.params.data_ptr()),
+            ctypes.c_void_p(eng.grad_local.data_ptr()), ctypes.byref(eng._outputs(True, False)),
+            ctypes.c_void_p(eng.workspace.data_ptr()), eng._stream(), ev.ev, NEV, kn,
+            ctypes.byref(nk)))
+        for i in range(nk.value):
+            n = kn[i].decode()
+            if n not in acc:
+                acc[n] = 0.0
+                order.append(n)
+            acc[n] += ev.elapsed_ms(i, i + 1)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if not eng.xgmi:         # xGMI: adam() exchanges + updates in one kernel
+            eng.allreduce()
+        eng.adam()
+        e1.record()
+        tails.append((e0, e1))
+    torch.cuda.synchronize(dev)
+    kern_ms = {n: acc[n] / nev for n in order}
+    tail_ms = sum(a.elapsed_time(b) for a, b in tails) / nev
+    return kern_ms, tail_ms
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -274,11 +349,18 @@ def main():
     ap.add_argument("--batch", type=int, default=100, help="commits per GPU")
     ap.add_argument("--ne", type=int, default=200)
     ap.add_argument("--nc", type=int, default=74)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (upload timing, steady state, "
+                         "per-kernel events + roofline, DP tail, --e2e loop, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (probs, stats, params) as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-steps", type=int, default=6)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full, skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly")
     ap.add_argument("--no-steady", action="store_true",
-                    help="skip the steady-state re-timing after the clock-ramp warm-up")
+                    help="with --full, skip the steady-state re-timing after the clock-ramp "
+                         "warm-up")
     ap.add_argument("--graph-steps", type=int, default=50,
                     help="training steps captured per HIP graph (a divisor of --steps)")
     ap.add_argument("--variant", type=int, default=2, choices=(1, 2, 3, 4),
@@ -296,7 +378,7 @@ def main():
     ap.add_argument("--xkind", default="int10", choices=("int10", "real"),
                     help="node attributes: integers 0..9, or Ne distinct signed reals")
     ap.add_argument("--e2e", type=int, default=50, metavar="EPOCHS",
-                    help="also time graph2graph.train (the main.py --Type train loop) for "
+                    help="with --full, time graph2graph.train (the main.py --Type train loop) for "
                          "EPOCHS epochs of one --batch-commit step each (0: skip)")
     args = ap.parse_args()
 
@@ -344,12 +426,14 @@ def main():
         # sharing a device compete for its CUs, so one block per commit
         eng.set_split(False)
     eng.set_params(layout.init_flat(0, v))
-    eng.upload(cb)                               # warm the upload / prepare path once
-    torch.cuda.synchronize(dev)
-    t_up = time.perf_counter()
     db = eng.upload(cb)                          # host arrays -> HBM + hdg_prepare
     torch.cuda.synchronize(dev)
-    upload_ms = 1e3 * (time.perf_counter() - t_up)
+    upload_ms = None
+    if args.full:                                # the first upload warmed the path: time one
+        t_up = time.perf_counter()
+        db = eng.upload(cb)
+        torch.cuda.synchronize(dev)
+        upload_ms = 1e3 * (time.perf_counter() - t_up)
 
     def barrier():
         if launched:
@@ -391,6 +475,8 @@ def main():
     elapsed = timed()
     value = world * B * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs:                        # the last timed step's, before any other step
+        dump_outputs(args.dump_outputs, fetch_outputs(eng), rank, world)
 
     # Steady state, reported beside the headline: the device reaches its steady clocks only
     # after a few ms of back-to-back steps (20-step regions right after start-up: 0.0576,
@@ -398,7 +484,7 @@ def main():
     # more seconds of steps the same K steps are timed again.  The replay count is agreed
     # across ranks (every rank replays the same graphs: their exchanges must pair up).
     steady = None
-    if not args.no_steady:
+    if args.full and not args.no_steady:
         t_w = time.perf_counter()
         step()
         torch.cuda.synchronize(dev)
@@ -418,59 +504,29 @@ def main():
                           "steps (the device's clock ramp); not the headline" % (
                               args.steps, 1e3 * WARM_S)}
 
-    # per-kernel durations: HIP events on the launch stream after every kernel launch of
-    # the step (hdg_fwd_bwd_kernel_events), eager launches, a separate instrumented pass
-    # with the training step's outputs (probs, as the training sess.run fetches; no logits)
-    import ctypes
-    NEV = 40
-    ev = _lib.HipEvents(NEV)
-    kn = (ctypes.c_char_p * (NEV - 1))()
-    nk = ctypes.c_int32()
-    acc, order = {}, []
-    nev = max(10, min(args.steps, 50))
-    tails = []                  # data parallel: the all-reduce + Adam tail after fwd_bwd
-    for _ in range(nev):
-        bstruct = db.struct()
-        _lib.check(eng.lib.hdg_fwd_bwd_kernel_events(
-            ctypes.byref(eng.shape), ctypes.byref(bstruct), ctypes.c_void_p(eng.params.data_ptr()),
-            ctypes.c_void_p(eng.grad_local.data_ptr()), ctypes.byref(eng._outputs(True, False)),
-            ctypes.c_void_p(eng.workspace.data_ptr()), eng._stream(), ev.ev, NEV, kn,
-            ctypes.byref(nk)))
-        for i in range(nk.value):
-            n = kn[i].decode()
-            if n not in acc:
-                acc[n] = 0.0
-                order.append(n)
-            acc[n] += ev.elapsed_ms(i, i + 1)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        if not eng.xgmi:         # xGMI: adam() exchanges + updates in one kernel
-            eng.allreduce()
-        eng.adam()
-        e1.record()
-        tails.append((e0, e1))
-    torch.cuda.synchronize(dev)
-    kern_ms = {n: acc[n] / nev for n in order}
-    tail_ms = sum(a.elapsed_time(b) for a, b in tails) / nev
+    kern_ms, tail_ms = kernel_events(eng, db, max(10, min(args.steps, 50)), dev) if args.full \
+        else (None, None)
 
     if rank != 0:
         torch.distributed.destroy_process_group()
         return
     path_name = {_lib.PATH_FUSED: "fused", _lib.PATH_GENERAL: "general"}[eng.path]
-    dom = max(kern_ms, key=kern_ms.get)          # the dominant kernel of the step
-    roofline = build_roofline(dom, kern_ms, v, path_name, ne, nc, B, default_data, args.hunk)
+    roofline = None
+    if args.full:
+        dom = max(kern_ms, key=kern_ms.get)      # the dominant kernel of the step
+        roofline = build_roofline(dom, kern_ms, v, path_name, ne, nc, B, default_data, args.hunk)
     # the general path's hunk pair-sum form this run used (include/hdgnn.h's rule by Nc)
     hunk_form = args.hunk if args.hunk != "auto" else (
         "tiled" if nc >= _lib.HUNK_TILED_MIN_NC else
         "sorted" if nc >= _lib.HUNK_SORTED_MIN_NC else "dense") + " (auto)"
     e2e = None
-    if world == 1 and args.e2e > 0:
+    if args.full and world == 1 and args.e2e > 0:
         try:                     # a side measurement: never costs the bench line
             e2e = e2e_train(B, ne, nc, v, args.e2e, dev)
         except Exception as ex:  # noqa: BLE001
             e2e = {"error": "%s: %s" % (type(ex).__name__, ex)}
     cpu = None
-    if world == 1 and not args.no_cpu and v == 2:
+    if args.full and world == 1 and not args.no_cpu and v == 2:
         threads = min(16, os.cpu_count() or 1)
         cpu = cpu_baseline(cb, args.cpu_steps, threads)
     ndev = min(world, torch.cuda.device_count()) if launched else 1
@@ -480,7 +536,7 @@ def main():
             "warmup_note": "exactly the requested W untimed training steps before the timed "
                            "region (plus the HIP-graph capture's state-neutral warm step)",
             "ms_per_step": round(ms_per_step, 5),
-            "steady_state": steady,
+            **({"steady_state": steady} if args.full else {}),
             **({"rehearsal": "%d ranks share %d device(s): not a %d-GPU measurement" % (
                 world, ndev, world)} if shared else {}),
             "allreduce": {"xgmi": "in-kernel xGMI exchange of the flat gradient per step "
@@ -506,15 +562,18 @@ def main():
                           if shared else {}),
                        **({"hunk_sums": hunk_form} if eng.path == _lib.PATH_GENERAL else {}),
                        **({} if default_data else {"data_knobs": knobs})},
-            "roofline": roofline, "cpu_baseline": cpu,
             "dp": {"allreduce": eng.allreduce_kind, "selftest": eng.allreduce_selftest,
-                   "tail_ms_per_step": round(tail_ms, 5),
-                   "tail": "k_grad_reduce excluded; xgmi: hdg_adam_dp (exchange + Adam, the "
-                           "k_dp_tail work); rccl: all_reduce + hdg_adam_tf"} if launched else None,
+                   **({"tail_ms_per_step": round(tail_ms, 5),
+                       "tail": "k_grad_reduce excluded; xgmi: hdg_adam_dp (exchange + Adam, "
+                               "the k_dp_tail work); rccl: all_reduce + hdg_adam_tf"}
+                      if args.full else {})} if launched else None}
+    if args.full:
+        line.update({
+            "roofline": roofline, "cpu_baseline": cpu,
             "upload_prepare_ms": round(upload_ms, 3),
             "pcie_inclusive_commits_per_s": round(world * B / ((ms_per_step + upload_ms) * 1e-3), 1),
             "kernels_ms": {k: round(t, 5) for k, t in kern_ms.items()},
-            "fwd_bwd_ms": round(sum(kern_ms.values()), 5)}
+            "fwd_bwd_ms": round(sum(kern_ms.values()), 5)})
     if e2e:
         line["e2e"] = e2e
     print(json.dumps(line), flush=True)

@@ -13,7 +13,7 @@ run() {   # run <tag> <bench args...>
   [ $rc -eq 0 ] || exit $rc
 }
 for t in ${*:-$ORDER}; do
-  run $t ${CFG[$t]}
+  run $t --full ${CFG[$t]}
 done
-[ -z "$*" ] && HDG_FUSED_SPLIT=0 run glide_oneblock
+[ -z "$*" ] && HDG_FUSED_SPLIT=0 run glide_oneblock --full
 exit 0

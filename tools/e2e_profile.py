@@ -1,5 +1,5 @@
 """Host-side cProfile of graph2graph.train (the main.py --Type train loop) at glide, one
-B = 100 step per epoch, as bench.py --e2e runs it (GPU box):
+B = 100 step per epoch, as bench.py --full --e2e runs it (needs an MI355X):
     python tools/e2e_profile.py [epochs]
 Prints the wall time per epoch and the functions with the most own time."""
 import contextlib

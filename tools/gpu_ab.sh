@@ -11,6 +11,7 @@ for tag in "$@"; do
     rc=$?; echo "$tag tests: $(tail -1 gpurun_out/ab/$tag.tests.log)"; [ $rc -ne 0 ] && exit $rc
   fi
 done
+BARGS="--full $BARGS"     # the lines below read steady_state and kernels_ms
 for rep in 1 2; do
 for tag in "$@"; do
   for v in ${VARIANTS:-2 4}; do

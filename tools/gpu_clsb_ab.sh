@@ -22,7 +22,7 @@ for rep in 1 2; do
   for tag in orig "$@"; do
     for cfg in "${CFGS[@]}"; do
       name=${cfg%%:*}; args=${cfg#*:}
-      HDG_LIB_PATH=$(lp $tag) timeout -k 10 200 python bench.py --no-cpu --e2e 0 --steps 20 --warmup 5 $args \
+      HDG_LIB_PATH=$(lp $tag) timeout -k 10 200 python bench.py --full --no-cpu --e2e 0 --steps 20 --warmup 5 $args \
           > gpurun_out/clsb/$tag.$name.log 2>&1 || { tail -5 gpurun_out/clsb/$tag.$name.log; exit 1; }
       grep -h '^{' gpurun_out/clsb/$tag.$name.log | python3 -c '
 import json, sys

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
     tests/test_xgmi_gpu.py tests/test_rccl_gpu.py > gpurun_out/dp/pytest_dp.log 2>&1 \
     || { tail -40 gpurun_out/dp/pytest_dp.log; exit 1; }
 tail -3 gpurun_out/dp/pytest_dp.log
-timeout -k 10 300 python bench.py --gpus 4 --steps 20 --warmup 5 --no-cpu --e2e 0 \
+timeout -k 10 300 python bench.py --gpus 4 --steps 20 --warmup 5 --full --no-cpu --e2e 0 \
     > gpurun_out/dp/bench_gpus4.log 2>&1 || { tail -40 gpurun_out/dp/bench_gpus4.log; exit 1; }
 grep '^{' gpurun_out/dp/bench_gpus4.log | cut -c1-600
 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 \

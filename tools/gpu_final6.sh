@@ -17,10 +17,10 @@ if [ "$1" = a ]; then
       python -u -m pytest tests -m gpu -x -q --timeout 400 --timeout-method thread
   step smoke 300 python __graft_entry__.py smoke
   step bench_driver_cmd 300 python bench.py --gpus 1 --steps 20 --warmup 5
-  step bench_default 600 python bench.py
+  step bench_default 600 python bench.py --full
 else
   bash tools/bench_matrix.sh || exit $?
-  step bench_gpus2 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu --e2e 0
-  step bench_gpus4 300 python bench.py --gpus 4 --steps 20 --warmup 5 --no-cpu --e2e 0
+  step bench_gpus2 300 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu --e2e 0
+  step bench_gpus4 300 python bench.py --gpus 4 --steps 20 --warmup 5 --full --no-cpu --e2e 0
   step phases 200 python tools/mid_phases.py
 fi

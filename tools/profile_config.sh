@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 echo "$*" > "$OUT/args.txt"
-BENCH="$R/bench.py --no-cpu --e2e 0 $*"
+BENCH="$R/bench.py --full --no-cpu --e2e 0 $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- \
     python3 $BENCH --steps 20 --warmup 5 > "$OUT/bench_trace.log" 2>&1 || exit $?
 echo "$TAG trace ok"
