@@ -1,6 +1,7 @@
-"""Literal incidence-matrix restatement of model_2 (TEST INFRASTRUCTURE ONLY).
+"""Literal incidence-matrix restatement of model_1..4 (TEST INFRASTRUCTURE ONLY).
 
-Runs the reference graph op for op (model_2.py:86-130): one-hot incidence
+Runs the reference graph op for op (model_2.py:86-130; the other variants'
+build_model at model_1.py:75-91, model_3.py:82-102, model_4.py:84-103): one-hot incidence
 tensors Es/Et (B,Ne,Ner), Cs/Ct (B,Nc,Ncr), Esc/Etc (B,Nc,Ner) and batched
 matmuls / transposes / concats exactly as written, in torch on the CPU.  It
 performs the same dense FLOPs as the TF1 CPU graph, so it is what bench.py
@@ -49,8 +50,9 @@ def build_dense(x, a, y, hid, nlen, dtype=torch.float32):
                 Ct=Ct, Esc=Esc, Etc=Etc)
 
 
-def forward(P, D, Bsz, Ne, Nc):
-    """model_2 build_model, literally.  P: short-key -> tensor, D: build_dense()."""
+def forward(P, D, Bsz, Ne, Nc, variant=2):
+    """build_model of model_<variant>, literally.  P: short-key -> tensor (that variant's
+    variables only: loss_para runs over all of them), D: build_dense()."""
     Ner, Ncr = Ne * (Ne - 1), Nc * (Nc - 1)
     Es, Et, E_edge = D["Es"], D["Et"], D["E_edge"]
     O = D["E_node"]
@@ -60,13 +62,35 @@ def forward(P, D, Bsz, Ne, Nc):
 
     B_1 = marshalling_B1(O, E_edge)                                          # (B,4,Ner)
     Bt = B_1.transpose(1, 2).reshape(Bsz * Ner, 4)                           # 164-165
-    h1 = torch.relu(Bt @ P["E1.w1"] + P["E1.b1"])                            # 170
-    h5 = (h1 @ P["E1.w5"] + P["E1.b5"]).reshape(Bsz, Ner, 20).transpose(1, 2)  # 175-178
-    E_bar = h5 @ Es.transpose(1, 2) + h5 @ Et.transpose(1, 2)               # 186
-    Cc = torch.cat([O, E_bar], 1).transpose(1, 2).reshape(Bsz * Ne, 21)      # 188, 193-194
-    hh = torch.relu(Cc @ P["E3.w1"] + P["E3.b1"])                            # 199
-    O2 = torch.relu(hh @ P["E3.w2"] + P["E3.b2"]).reshape(Bsz, Ne, 1).transpose(1, 2)  # 202-204
-    B_2 = marshalling_B1(O2, E_edge)                                         # 94
+    O2 = None
+    if variant in (2, 4):        # node translation (model_2.py:89-91, model_4.py:87-89)
+        h1 = torch.relu(Bt @ P["E1.w1"] + P["E1.b1"])                        # 170
+        h5 = (h1 @ P["E1.w5"] + P["E1.b5"]).reshape(Bsz, Ner, 20).transpose(1, 2)  # 175-178
+        E_bar = h5 @ Es.transpose(1, 2) + h5 @ Et.transpose(1, 2)           # 186
+        Cc = torch.cat([O, E_bar], 1).transpose(1, 2).reshape(Bsz * Ne, 21)  # 188, 193-194
+        hh = torch.relu(Cc @ P["E3.w1"] + P["E3.b1"])                        # 199
+        O2 = torch.relu(hh @ P["E3.w2"] + P["E3.b2"]).reshape(Bsz, Ne, 1).transpose(1, 2)  # 202-204
+    E_edge2 = None
+    if variant in (3, 4):        # edge translation (model_3.py:91-93, model_4.py:92-94)
+        # mlp_entityedge_B1 (model_4.py:206-243; mlp_edge_B1, model_3.py:205-242)
+        w1 = torch.cat([P["EE.w11"], P["EE.w11"], P["EE.w12"]], 0)           # 221: shared w1_1
+        q1 = torch.relu(Bt @ w1 + P["EE.b1"])                                # 224
+        q2 = (q1 @ P["EE.w2"] + P["EE.b2"]).reshape(Bsz, Ner, 20).transpose(1, 2)  # 229-231
+        qbar1 = q2 @ Es.transpose(1, 2)                                      # 236
+        qbar2 = q2 @ Et.transpose(1, 2)                                      # 238
+        eff_e = qbar1 @ Es + qbar2 @ Et                                      # 241  (B,20,Ner)
+        C_R = torch.cat([E_edge, eff_e], 1)                                  # agg 282-284
+        # mlp2_entityedge_B1 (286-304)
+        Ce = C_R.transpose(1, 2).reshape(Bsz * Ner, 22)                      # 289-290
+        r1 = torch.relu(Ce @ P["EC.w1"] + P["EC.b1"])                        # 296
+        r2 = (r1 @ P["EC.w2"] + P["EC.b2"]).reshape(Bsz, Ner, 2).transpose(1, 2)   # 301-302
+        E_edge2 = torch.softmax(r2, 1)                                       # 303
+    if variant in (1, 3):
+        B_2 = B_1                                     # model_1.py:76, model_3.py:97: B_1 goes on
+    elif variant == 2:
+        B_2 = marshalling_B1(O2, E_edge)                                     # model_2.py:94
+    else:
+        B_2 = marshalling_B1(O2, E_edge2)                                    # model_4.py:97
     # marshalling_B2 (146-159)
     B_t = B_2.transpose(1, 2)
     neighbors = D["Esc"] @ B_t + D["Etc"] @ B_t                              # (B,Nc,4)

@@ -110,10 +110,18 @@ def unflatten(vec, variant=2):
 # ----------------------------------------------------------------------------
 # forward
 # ----------------------------------------------------------------------------
-def _mlp_pair_entity(P, B1):
+def _mlp_pair_entity(P, B1, trace=None):
     """mlp_entity_B1 (model_2.py:161-179): relu(B@w1+b1)@w5+b5, no output relu."""
-    h1 = torch.relu(B1 @ P["E1.w1"] + P["E1.b1"])
-    return h1 @ P["E1.w5"] + P["E1.b5"]
+    z1 = _pre(trace, "E1", B1 @ P["E1.w1"] + P["E1.b1"])
+    return torch.relu(z1) @ P["E1.w5"] + P["E1.b5"]
+
+
+def _pre(trace, layer, z):
+    """Record a first layer's pre-activations (the relu's argument) for the tests that
+    need to know which hidden units are on; the value passes through unchanged."""
+    if trace is not None:
+        trace[layer] = z.detach()
+    return z
 
 
 def _row_col_sum(vals, I, J, n):
@@ -133,10 +141,12 @@ def _row_sum(vals, I, n):
     return out
 
 
-def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
+def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64, trace=None):
     """Returns dict(logits (B,Pc,2), probs, ce, loss_map, loss_para, total, theta).
 
     P: dict short_key -> torch tensor (leaf, requires_grad for gradients).
+    trace: optional dict, filled with every first layer's pre-activations
+    ("E1", "E3", "EE", "EC", "H1", "H2" -> tensor (..., 20)).
     """
     x = torch.as_tensor(np.asarray(x), dtype=dtype)
     a = np.asarray(a)
@@ -159,10 +169,10 @@ def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
 
     if variant in (2, 4):
         # mlp_entity_B1 -> agg_entity_B1 -> mlp2_entity_B1 (model_2.py:89-91)
-        e = _mlp_pair_entity(P, B1)                                        # (B, Pe, 20)
+        e = _mlp_pair_entity(P, B1, trace)                                       # (B, Pe, 20)
         Ebar = _row_col_sum(e, I, J, Ne)                                   # (B, Ne, 20)
         Cin = torch.cat([x[..., None], Ebar], -1)                          # concat [O, E_bar] (188)
-        h = torch.relu(Cin @ P["E3.w1"] + P["E3.b1"])
+        h = torch.relu(_pre(trace, "E3", Cin @ P["E3.w1"] + P["E3.b1"]))
         xp = torch.relu(h @ P["E3.w2"] + P["E3.b2"])[..., 0]              # relu on output (202)
     else:
         xp = None
@@ -171,7 +181,7 @@ def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
     if variant in (3, 4):
         # mlp_entityedge_B1 (model_4.py:206-243): shared w1 = [w1_1; w1_1; w1_2]
         w1 = torch.cat([P["EE.w11"], P["EE.w11"], P["EE.w12"]], 0)
-        k1 = torch.relu(B1 @ w1 + P["EE.b1"])
+        k1 = torch.relu(_pre(trace, "EE", B1 @ w1 + P["EE.b1"]))
         k2 = k1 @ P["EE.w2"] + P["EE.b2"]                                  # (B, Pe, 20)
         Srow = _row_sum(k2, I, Ne)                                         # h2 Es^T
         Tcol = _row_sum(k2, J, Ne)                                         # h2 Et^T
@@ -179,7 +189,7 @@ def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
         # agg_entityedge_B1 (282-284): concat [E_edge, effects]
         CR = torch.cat([E_edge, eff], -1)
         # mlp2_entityedge_B1 (286-304)
-        zl = torch.relu(CR @ P["EC.w1"] + P["EC.b1"]) @ P["EC.w2"] + P["EC.b2"]
+        zl = torch.relu(_pre(trace, "EC", CR @ P["EC.w1"] + P["EC.b1"])) @ P["EC.w2"] + P["EC.b2"]
         probs_e = torch.softmax(zl, -1)
         if variant == 4:
             E_edge2 = probs_e                                              # model_4.py:97
@@ -201,7 +211,7 @@ def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
     B3 = torch.cat([nbr[:, tIp], nbr[:, tJq], C_edge], -1)                # (B, Pc, 10)
 
     # mlp_hunk_B2 (model_2.py:245-277)
-    g = torch.relu(B3 @ P["H1.w1"] + P["H1.b1"]) @ P["H1.w2"] + P["H1.b2"]
+    g = torch.relu(_pre(trace, "H1", B3 @ P["H1.w1"] + P["H1.b1"])) @ P["H1.w2"] + P["H1.b2"]
     S = _row_sum(g, Ip, Nc)                                                # (g Cs^T)
     T = _row_sum(g, Jq, Nc)                                                # (g Ct^T)
     eff_h = S[:, tIp] + T[:, tJq]                                          # (.)Cs + (.)Ct (275)
@@ -209,7 +219,7 @@ def forward(P, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
     # agg_edge_B1 (279-281): labels first
     HR = torch.cat([C_edge, eff_h], -1)                                    # (B, Pc, 22)
     # mlp_hunkedge_B2 (304-324)
-    logits = torch.relu(HR @ P["H2.w1"] + P["H2.b1"]) @ P["H2.w2"] + P["H2.b2"]
+    logits = torch.relu(_pre(trace, "H2", HR @ P["H2.w1"] + P["H2.b1"])) @ P["H2.w2"] + P["H2.b2"]
     probs = torch.softmax(logits, -1)
 
     # losses (model_2.py:115-130, 326-333)
@@ -234,10 +244,10 @@ def to_torch_params(params, dtype=torch.float64, requires_grad=True):
             for k, v in params.items()}
 
 
-def loss_and_grads(params, x, a, y, hid, nlen, variant=2, dtype=torch.float64):
+def loss_and_grads(params, x, a, y, hid, nlen, variant=2, dtype=torch.float64, trace=None):
     """Forward + autograd backward of train_loss; returns (out, grads dict numpy)."""
     P = to_torch_params(params, dtype)
-    out = forward(P, x, a, y, hid, nlen, variant, dtype)
+    out = forward(P, x, a, y, hid, nlen, variant, dtype, trace)
     out["total"].backward()
     grads = {k: P[k].grad.detach().numpy().copy() for k in P}
     det = {k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in out.items()

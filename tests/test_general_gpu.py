@@ -83,9 +83,10 @@ def _grad_close(g_eng, g_ref, v):
     assert not bad, "gradient mismatch:\n  " + "\n  ".join(bad)
 
 
-def _run_and_check(cb, v, seed, path=GEN, flags=0):
+def _run_and_check(cb, v, seed, path=GEN, flags=0, flat=None):
     B, ne, nc = cb.B, cb.Ne, cb.Nc
-    flat = layout.init_flat(seed, v)
+    if flat is None:
+        flat = layout.init_flat(seed, v)
     eng = _engine(B, ne, nc, v, path, flags)
     eng.set_params(flat)
     db = eng.upload(cb)
