@@ -59,6 +59,9 @@ ABI_VERSION = 9
 # gradient trailer (include/hdgnn.h): grad = [P parameter gradients | TRAILER slots]
 TRAILER, TR_CE, TR_COUNT, TR_FAULT = 8, 0, 1, 4
 STATUS_XCH_TIMEOUT, STATUS_DP_TIMEOUT = 1, 2
+# hdg_eval's per-commit table (include/hdgnn.h): ev[B][EV_SLOTS] u64
+EV_SLOTS, EV_TP, EV_FP, EV_FN, EV_TN, EV_U2, EV_NAN = 8, 0, 1, 2, 3, 4, 5
+EVAL_CHUNK = 16384     # relations per block of the evaluation kernel
 
 
 def trailer_count(tr):
@@ -76,7 +79,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_pack_classes", "hdg_crc32c", "hdg_fwd_bwd_kernel_events",
            "hdg_bundle_write", "hdg_ckpt_writer_create", "hdg_ckpt_writer_submit",
            "hdg_ckpt_writer_flush", "hdg_ckpt_writer_poll", "hdg_ckpt_writer_destroy", "hdg_memcpy_async",
-           "hdg_event_create", "hdg_event_record", "hdg_event_synchronize", "hdg_event_destroy"]
+           "hdg_event_create", "hdg_event_record", "hdg_event_synchronize", "hdg_event_destroy",
+           "hdg_eval"]
 
 _lib = None
 
@@ -115,6 +119,7 @@ def load(path=None):
     lib.hdg_adam_tf.argtypes = [P(Shape), P(State), vp, f32, vp, vp]
     lib.hdg_train_step.argtypes = [P(Shape), P(Batch), P(State), f32, P(Outputs), vp, vp, vp]
     lib.hdg_forward.argtypes = [P(Shape), P(Batch), vp, P(Outputs), vp, vp, vp]
+    lib.hdg_eval.argtypes = [P(Shape), P(Batch), vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

@@ -15,7 +15,7 @@ ARCH = "gfx950"
 
 
 def build(verbose=False, out=None, force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("hdgnn.hip", "wide.hip")]
+    srcs = [os.path.join(CSRC, f) for f in ("hdgnn.hip", "wide.hip", "eval.hip")]
     out = out or os.path.join(CSRC, "libhdgnn.so")
     deps = srcs + [os.path.join(CSRC, "hdgnn_internal.h"), os.path.join(ROOT, "include", "hdgnn.h")]
     extra = os.environ.get("HDG_HIPCC_FLAGS", "").split()   # experiments (A/B builds)

@@ -363,3 +363,24 @@ class Engine:
                                         ctypes.c_void_p(self.workspace.data_ptr()),
                                         self._stream()))
         return self.probs, self.logits, self.ce_sum
+
+    def evaluate(self, dbatch, probs=None):
+        """hdg_eval: the per-commit evaluation table of `probs` ([B][2][nc(nc-1)] fp32 on
+        this device; default self.probs as the last forward / fwd_bwd / train step left it)
+        against the batch's labels -> a fresh int64 device tensor [B][EV_SLOTS] (TP, FP,
+        FN, TN, U2, NAN; hdgnn.metrics.scores_from_counts turns it into scores).  Enqueued on
+        the current stream; nothing is copied to the host."""
+        self._check(dbatch)
+        probs = self.probs if probs is None else probs
+        if (probs.device != self.device or probs.dtype != torch.float32
+                or not probs.is_contiguous()
+                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
+            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
+                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        # the library writes u64 counts; every value is < 2^63, so int64 reads them as they are
+        ev = torch.empty(self.batch, _lib.EV_SLOTS, dtype=torch.int64, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_eval(ctypes.byref(self.shape), ctypes.byref(b),
+                                     ctypes.c_void_p(probs.data_ptr()),
+                                     ctypes.c_void_p(ev.data_ptr()), self._stream()))
+        return ev

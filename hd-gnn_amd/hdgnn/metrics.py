@@ -75,3 +75,89 @@ def AUC(label, real):
             auc += s
             count += 1
     return auc / count
+
+
+# ---------------------------------------------------------------------------------------
+# Counts-based evaluation of the trained classifier (not the reference's quirks above):
+# the integer table hdg_eval computes on the device (include/hdgnn.h, HDG_EV_*), its host
+# implementation, and the scores that follow from it.
+# ---------------------------------------------------------------------------------------
+EV_SLOTS, EV_TP, EV_FP, EV_FN, EV_TN, EV_U2, EV_NAN = 8, 0, 1, 2, 3, 4, 5
+
+
+def eval_counts(label_onehot, probs):
+    """(B, 2, R) one-hot labels and probabilities -> int64 (B, EV_SLOTS): per commit TP, FP,
+    FN, TN of the argmax prediction (class 1 when p1 > p0: np.argmax's tie rule), U2 = sum
+    over (positive, negative) pairs of 2 [s_p > s_n] + [s_p == s_n] with s = probs[:, 1], and
+    the number of relations with a NaN in either channel (counted in no other slot and in no
+    pair).  The host implementation of hdg_eval: the negatives' scores sorted once per commit,
+    np.searchsorted left and right for each positive."""
+    label = np.asarray(label_onehot)
+    probs = np.asarray(probs)
+    B = label.shape[0]
+    ev = np.zeros((B, EV_SLOTS), np.int64)
+    for b in range(B):
+        y = label[b, 1] > label[b, 0]
+        p0, p1 = probs[b, 0], probs[b, 1]
+        nan = np.isnan(p0) | np.isnan(p1)
+        ok = ~nan
+        pred = np.zeros(y.shape, bool)
+        pred[ok] = p1[ok] > p0[ok]
+        ev[b, EV_TP] = np.count_nonzero(ok & y & pred)
+        ev[b, EV_FP] = np.count_nonzero(ok & ~y & pred)
+        ev[b, EV_FN] = np.count_nonzero(ok & y & ~pred)
+        ev[b, EV_TN] = np.count_nonzero(ok & ~y & ~pred)
+        ev[b, EV_NAN] = np.count_nonzero(nan)
+        neg = np.sort(p1[ok & ~y])
+        pos = p1[ok & y]
+        lb = np.searchsorted(neg, pos, side="left").astype(np.int64)
+        ub = np.searchsorted(neg, pos, side="right").astype(np.int64)
+        ev[b, EV_U2] = int((2 * lb + (ub - lb)).sum())
+    return ev
+
+
+def _ratio(num, den):
+    """num / den in float64, nan where den == 0 (no warning)."""
+    num = np.asarray(num, np.float64)
+    den = np.asarray(den, np.float64)
+    out = np.full(np.broadcast(num, den).shape, np.nan)
+    np.divide(num, den, out=out, where=den != 0)
+    return out
+
+
+def _nanmean(v):
+    v = np.asarray(v, np.float64).reshape(-1)
+    v = v[~np.isnan(v)]
+    return float(v.mean()) if v.size else float("nan")
+
+
+def scores_from_counts(ev):
+    """(n_commits, EV_SLOTS) integer table -> dict of scores.
+
+    acc / precision / recall / f1: pooled over all relations of all commits;
+    acc_mean / precision_mean / recall_mean / f1_mean: the mean of the per-commit ratios over
+    the commits where the ratio is defined.  A ratio with a zero denominator is nan.
+    auc: mean over commits with both classes (P = TP + FN > 0 and N = FP + TN > 0) of
+    U2 / (2 P N) in float64, nan when there is no such commit; auc_commits: how many were
+    scored; nan_relations: relations left out because a probability was NaN."""
+    ev = np.asarray(ev).reshape(-1, EV_SLOTS).astype(np.int64)
+    tp, fp, fn, tn = (ev[:, k] for k in (EV_TP, EV_FP, EV_FN, EV_TN))
+
+    def four(tp, fp, fn, tn):
+        return (_ratio(tp + tn, tp + fp + fn + tn), _ratio(tp, tp + fp), _ratio(tp, tp + fn),
+                _ratio(2 * tp, 2 * tp + fp + fn))
+
+    names = ("acc", "precision", "recall", "f1")
+    out = {}
+    for n, pooled, per in zip(names, four(tp.sum(), fp.sum(), fn.sum(), tn.sum()),
+                              four(tp, fp, fn, tn)):
+        out[n] = float(pooled)
+        out[n + "_mean"] = _nanmean(per)
+    P, N = tp + fn, fp + tn
+    both = (P > 0) & (N > 0)
+    auc = ev[both, EV_U2].astype(np.float64) / (2.0 * P[both].astype(np.float64)
+                                                * N[both].astype(np.float64))
+    out["auc"] = float(auc.mean()) if auc.size else float("nan")
+    out["auc_commits"] = int(both.sum())
+    out["nan_relations"] = int(ev[:, EV_NAN].sum())
+    return out

@@ -553,6 +553,51 @@ class graph2graph(object):
             eng.beta_pow.copy_(torch.from_numpy(np.asarray(bp, np.float32)))
         return True
 
+    # ------------------------------------------------------------------ evaluate
+    def evaluate(self, args, part="test"):
+        """Score the trained classifier on the test (or train) split without moving the
+        probabilities: per batch Engine.forward then Engine.evaluate (hdg_eval), and only the
+        per-commit integer rows (include/hdgnn.h, HDG_EV_*) come to the host.  Not a reference
+        flow: unlike test() it restores the checkpoint from where train() saves it, and its
+        scores are the usual ones (metrics.scores_from_counts), not EvaluationFuncs' quirks.
+        Same batches as test(): shard_plan over the part, the maps of the first Mini_batch
+        commits, remainder commits dropped.  -> (scores dict, int64 table [n_commits][8]);
+        rank 0 prints the scores and writes the table to
+        outputSelf/<Repo>/model_<v>/<Step>/eval_counts<Ne>.npy."""
+        import torch
+        if part not in ("train", "test"):
+            raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
+        _, _, train, test, maps = self._compact()
+        if self.load(self.checkpoint_dir):
+            print(" [*] Load SUCCESS")
+        else:
+            print(" [!] Load failed...")
+        eng = self.engine
+        rows = []
+        for db in self._device_batches(train if part == "train" else test, maps):
+            eng.forward(db)
+            rows.append(eng.evaluate(db))
+        nb = len(rows)
+        table = (torch.stack(rows).cpu().numpy() if nb
+                 else np.zeros((0, self.local_batch, _lib.EV_SLOTS), np.int64))
+        eng.check_status()
+        if self.world > 1 and nb:      # rank-major (W nb, lb, 8) -> batch-major commit order
+            table = self._gather(table).reshape(self.world, nb, self.local_batch, _lib.EV_SLOTS)
+            table = table.transpose(1, 0, 2, 3)
+        table = np.ascontiguousarray(table.reshape(-1, _lib.EV_SLOTS)).astype(np.int64)
+        scores = metrics.scores_from_counts(table)
+        if self.rank == 0:
+            step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
+            os.makedirs(step_dir, exist_ok=True)
+            np.save(step_dir + 'eval_counts' + str(self.Ne) + '.npy', table)
+            for name in ("acc", "precision", "recall", "f1"):
+                print('eval %s: %s (per-commit mean %s)' % (name, scores[name],
+                                                            scores[name + "_mean"]))
+            print('eval auc: %s (%d of %d commits)' % (scores["auc"], scores["auc_commits"],
+                                                       len(table)))
+            print('eval nan relations: %d' % scores["nan_relations"])
+        return scores, table
+
     # ------------------------------------------------------------------ test
     def test(self, args):
         _, C_edge_test, _, test, maps = self._compact()

@@ -6,6 +6,8 @@ MI355X instead of a TF1 session.
     python hd-gnn_amd/main.py --Type train [--epoch 50 --Mini_batch 50 ...]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
         hd-gnn_amd/main.py --Type train          # data parallel over N GPUs (RCCL)
+    python hd-gnn_amd/main.py --Type eval      # accuracy / precision / recall / F1 / ROC-AUC
+                                               # of the trained model, computed on the device
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -103,6 +105,8 @@ def main(argv=None, model_cls=None):
             model.train(args)
         if args.Type == 'test':
             model.test(args)
+        if args.Type == 'eval':      # not in the reference: on-device scores of the trained model
+            model.evaluate(args)
 
 
 if __name__ == '__main__':

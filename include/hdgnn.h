@@ -230,6 +230,40 @@ int hdg_forward(const hdg_shape* shape, const hdg_batch* batch, const float* par
                 hdg_outputs* out, float* ce_sum, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * On-device evaluation (csrc/eval.hip).  The reference scores a model on the host after
+ * fetching every probability (EvaluationFuncs.py on C_edge_output2, model_2.py:486-548);
+ * hdg_eval reduces the probabilities where they are to HDG_EV_SLOTS integers per commit,
+ * from which accuracy, precision, recall, F1 and the exact ROC-AUC follow
+ * (hdgnn.metrics.scores_from_counts): AUC of a commit = U2 / (2 P N), P = TP + FN,
+ * N = FP + TN (ties count half, as sklearn.metrics.roc_auc_score).
+ *
+ *   probs   the [B][2][nc(nc-1)] array hdg_forward / hdg_fwd_bwd write (any device array
+ *           of that shape); the score of relation r is probs[b][1][r]
+ *   batch   only batch->ybits is read: the label of relation r = (i, j) (i = r / (nc-1),
+ *           jj = r % (nc-1), j = jj + (jj >= i)) is bit j of ybits[b][i]
+ *   ev      [batch][HDG_EV_SLOTS] u64, zeroed by the call itself
+ * Predicted class 1 means p1 > p0 (np.argmax: a tie picks class 0, the rule of the
+ * HDG_TR_COUNT trailer count, which TP + TN summed over the commits equals for a launch
+ * without NaNs).  Only shape->batch and shape->nc are used.  Integer sums throughout: the
+ * same bits on every run, whatever order the blocks run in.  One launch after a memset
+ * node, no workspace, no host synchronisation.                                          */
+#define HDG_EV_SLOTS 8
+#define HDG_EV_TP 0      /* label 1, predicted 1                                   */
+#define HDG_EV_FP 1      /* label 0, predicted 1                                   */
+#define HDG_EV_FN 2      /* label 1, predicted 0                                   */
+#define HDG_EV_TN 3      /* label 0, predicted 0                                   */
+#define HDG_EV_U2 4      /* sum over (positive p, negative n) pairs of the commit of
+                            2*[s_p > s_n] + [s_p == s_n], s = probs[b][1][r]       */
+#define HDG_EV_NAN 5     /* relations with a NaN in either channel: counted here and
+                            in no other slot, and in no pair                       */
+#define HDG_EVAL_CHUNK 16384   /* relations per block: each block sorts the negatives of
+                                  its chunk in LDS (64 KiB) and streams every positive of
+                                  the commit past them                              */
+
+int hdg_eval(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+             uint64_t* ev /* [batch][HDG_EV_SLOTS] */, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
  *
  * Instead of an RCCL call between hdg_fwd_bwd and hdg_adam_tf, the step's reduction
