@@ -11,9 +11,10 @@
 //   k_grad_reduce [P/64]    deterministic per-commit partial sum (fixed commit order)
 //   k_adam_tf     [1]       loss_para / loss_map gradients + TF1 ApplyAdam
 //
-// plus, once per uploaded batch, k_prep_sort / k_prep_counts (hdg_prepare): the
-// parameter-independent tables of a commit (x sort order, transposed class bits,
-// cross-graph count matrices).
+// This file holds the pair-tile engine, k_commit_step, kh_tile, those reduction / Adam
+// kernels, path resolution, sizing and the step entry points.  The once-per-batch tables
+// (hdg_prepare) are built in prep.hip, the data-parallel tails live in dp.hip, the
+// checkpoint writer in ckpt.cpp.
 //
 // Algebra used (exact up to fp32 re-association; derivation in DESIGN.md section 3):
 //   first-layer pre-activation of a pair MLP on [x_i, x_j, 1-a, a] = u_i + v_j + a*d;
@@ -22,60 +23,26 @@
 //   are prefix/suffix sums over the x-sorted order (O(Ne log nd) per hidden unit)
 //   plus sparse corrections for a = 1.  Hunk pairs run as dense register tiles.
 #include <hip/hip_runtime.h>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <type_traits>
 
 #include "hdgnn.h"
 #include "hdgnn_internal.h"
+#include "fused_tail.h"
 
 namespace {
 
-constexpr int HS = 20;              // h_size = De_e = De_er (model_2.py:163, 192, 247, 306)
-constexpr int NT_MID = 1024;        // k_commit_step block
-constexpr int KK_MID = 5;           // hidden units per pair-tile chunk in k_commit_step
+using namespace hdg;
 
-// model_2 flat parameter offsets (tf.global_variables order)
-namespace m2 {
-constexpr int E1_W1 = 0, E1_B1 = 80, E1_W5 = 100, E1_B5 = 500;
-constexpr int E3_W1 = 520, E3_B1 = 940, E3_W2 = 960, E3_B2 = 980;
-constexpr int H1_W1 = 981, H1_B1 = 1181, H1_W2 = 1201, H1_B2 = 1601;
-constexpr int H2_W1 = 1621, H2_B1 = 2061, H2_W2 = 2081, H2_B2 = 2121;
-constexpr int TH1 = 2123, TH2 = 2125, NP = 2127;
-}  // namespace m2
-constexpr int GRAD_LEN = m2::NP + HDG_TRAILER;
-constexpr int NPART = (GRAD_LEN + 3) & ~3;   // per-block partial row: NP grads + trailer
+constexpr int KK_MID = 5;           // hidden units per pair-tile chunk in k_commit_step
 
 // ------------------------------------------------------------------------------
 // cross-lane helpers (wave64)
 // ------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v),
-                                                               CTRL, 0xF, 0xF, false));
-}
-
-// Sum over a 16-lane DPP row; every lane of the row receives the total.
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dppf<0x140>(v);  // row_mirror        lane i <- 15-i
-  v += dppf<0x141>(v);  // row_half_mirror   lane i <- 7-i (per 8)
-  v += dppf<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dppf<0xB1>(v);   // quad_perm [1,0,3,2]
-  return v;
-}
-
 // row16_sum of N values as fused v_add_f32_dpp (one VALU op per value and step; the
 // compiler otherwise splits some into v_mov_dpp + v_add).  A DPP read needs 2 wait states
 // after the VALU write of its operand, and the compiler's hazard recognizer does not look
@@ -178,30 +145,6 @@ __device__ __forceinline__ void row16_sums(float (&v)[N]) {
   else row16_sum5(v + 3 * (G - 1));
 }
 
-// Sum over the 4 DPP rows of a wave for every lane column: lane l gets
-// v[l] + v[l^16] + v[l^32] + v[l^48].  v_permlane{32,16}_swap in the VALU (no LDS);
-// inline asm because the ROCm 7.2 builtins mis-assign the two results, with the two
-// wait states the swap needs after a VALU write of its operands inside the string.
-__device__ __forceinline__ float xrow_sum4(float v) {
-  float x = v, y = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-  const float s = x + y;
-  float p = s, q = s;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q));
-  return p + q;
-}
-
-__device__ __forceinline__ float wave_sum(float v) { return xrow_sum4(row16_sum(v)); }
-
-// x <-> y exchange of DPP rows: swap32 trades x's lanes 32-63 for y's lanes 0-31, swap16
-// x's rows 1, 3 for y's rows 0, 2 (v_permlane{32,16}_swap, same hazard handling as above)
-__device__ __forceinline__ void swap32(float& x, float& y) {
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-__device__ __forceinline__ void swap16(float& x, float& y) {
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-
 // Transposed cross-row reduction of N per-lane values: value n summed over the 4 DPP rows
 // (lane columns kept apart) with one swap + one add per PAIR of values at each of the two
 // levels, instead of two swaps + two adds per value.  Afterwards vector i (i < H2) holds
@@ -248,7 +191,7 @@ __device__ __forceinline__ void wave_sums(const float (&v)[N], const int lane, F
   for (int i = 0; i < H2; ++i) {
     float x = a[i], y = (i + H2 < H) ? a[i + H2] : 0.f;
     swap16(x, y);
-    b[i] = row16_sum(x + y);
+    b[i] = row16_sum<ROW_MIRROR>(x + y);
   }
   if ((lane & 15) == 0) {
     const int r = lane >> 4;
@@ -261,42 +204,9 @@ __device__ __forceinline__ void wave_sums(const float (&v)[N], const int lane, F
   }
 }
 
-__device__ __forceinline__ float reluf(float v) { return fmaxf(v, 0.f); }
-// ln x for x in [1, 2] (the two-class CE's log(1 + e^-|d|)): v_log_f32 (log2, ~1 ulp, no
-// denormal range to guard) times ln 2 -- 2 VALU ops where logf expands to a denormal-scaled,
-// split-constant sequence of ~11
-__device__ __forceinline__ float ln_1to2(float x) { return __builtin_amdgcn_logf(x) * 0.693147182f; }
-
 // padding / masked-row value of the pair-tile operands: far below any real pre-activation
 // but finite, so that z [z > 0] (MODE 0) and [z > 0] w (MODE 1, 2) are 0, never inf * 0
 constexpr float PADNEG = -1e30f;
-
-typedef float f2 __attribute__((ext_vector_type(2)));   // packed fp32 (v_pk_* ops)
-
-// [z > 0] for two lanes of a packed pair in ONE VALU op: clamp(z * 2^126, 0, 1) on
-// v_pk_mul_f32 (exact for every normal z; -0, NaN -> 0).  Used as step2(z) * w, which
-// needs w finite wherever z <= 0 (padding rows / columns are kept finite).
-__device__ __forceinline__ f2 step2(f2 z) {
-  f2 r;
-  asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(z), "v"((f2){0x1p126f, 0x1p126f}));
-  return r;
-}
-
-// [x + c > 0] for a packed pair in ONE op where only the step of the sum is used (the
-// backward passes' masks): clamp(fma(x, 2^64, c 2^64)).  The fma rounds the exact
-// (x + c) 2^64 once: 0 for x + c <= 0 (-0, NaN: 0), 1 for every x + c >= 2^-64, so it
-// differs from step2(fl(x + c)) only for 0 < x + c < 2^-64.  cs = c 2^64 (exact and finite
-// for |c| < 2^63; PADNEG 2^64 = -inf masks the pair).
-#ifndef HDG_STEPF
-#define HDG_STEPF 1
-#endif
-constexpr float STEP_S = 0x1p64f;
-__device__ __forceinline__ f2 stepf2(f2 x, f2 cs) {
-  f2 r;
-  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp"
-      : "=v"(r) : "v"(x), "s"((f2){STEP_S, STEP_S}), "v"(cs));
-  return r;
-}
 
 // q = r / d, rem = r % d for 0 <= r < 2^22, 1 <= d < 2^12: float estimate + one select
 // correction, 24-bit multiplies, no branches (keeps unrolled loads in flight)
@@ -557,7 +467,7 @@ __device__ __forceinline__ void pair_tile(
         const float z = at + fmaf(af, dkt, HB ? bcolt[c] : ld_tail<QM && (HDG_QTAIL & 1)>(Bj, ktl, grp));
         float e;
         if constexpr (MODE == 0) {
-          e = reluf(z);
+          e = relu(z);
         } else {
           const float w =
               (MODE == 1) ? (rwt + (HW ? wcolt[c] : ld_tail<QM && (HDG_QTAIL & 2)>(wc + j * LD, ktl, grp))) : g;
@@ -763,7 +673,7 @@ __device__ __forceinline__ void pair_tile32(
         const float z = at + fmaf(af, dkt, ld_tail<QM && (HDG_QTAIL & 1)>(Bj, ktl, grp));
         float e;
         if constexpr (MODE == 0) {
-          e = reluf(z);
+          e = relu(z);
         } else {
           const float w = (MODE == 1) ? (rwt + ld_tail<QM && (HDG_QTAIL & 2)>(wc + j * LD, ktl, grp)) : g;
           e = (z > 0.f) ? w : 0.f;
@@ -929,293 +839,6 @@ __device__ __forceinline__ float wave_incl_scan_dpp(float v) {
   return v;
 }
 
-__device__ __forceinline__ int top_pow2(int n) {   // largest power of two <= n (n >= 1)
-  return 1 << (31 - __builtin_clz((unsigned)n));
-}
-
-// ------------------------------------------------------------------------------
-// Prepared batch (hdg_prepare: once per uploaded batch, independent of the parameters).
-// Per commit, in 4-byte words:
-//   xsrt[NE4]    x sorted ascending            perm[NE4]  node at sorted slot m
-//   xu[NE4]      the nd distinct x values      cum[NE4+4] cum[q] = #nodes with x < xu[q]
-//   pxd[NE4+4]   f64 pxd[q] = sum of x over nodes with x < xu[q]      meta[4] = {nd}
-//   offr, offc   CSR offsets of the a = 1 neighbours of each node (rows of a, of a^T)
-//   lists        u8 ids of the row neighbours, padded like the row x-lists (xoffr)
-//   ks, kt       [Nc][Ne] u16 cross-graph counts (k_prep_counts)
-//   ncst[Nc][2]  f32 count of relations binned to hunk c with a = 0 / a = 1
-// ------------------------------------------------------------------------------
-using hdg::PrepLayout;
-using hdg::prep_layout;
-
-// sort x (stable rank count), distinct values + f64 prefix sums, transposed class bits
-__global__ __launch_bounds__(256) void k_prep_sort(const float* __restrict__ x,
-                                                   const uint32_t* __restrict__ abits,
-                                                   uint32_t* __restrict__ prep, int Ne, int Nc) {
-  const PrepLayout L = prep_layout(Ne, Nc);
-  const int b = blockIdx.x, t = threadIdx.x;
-  const int WE = (Ne + 31) >> 5;
-  __shared__ float xl[256], xsl[256];
-  __shared__ uint32_t al[256 * 8];
-  uint32_t* pb = prep + (size_t)b * L.words;
-  float* xsrt = (float*)(pb + L.xsrt);
-  int* perm = (int*)(pb + L.perm);
-  float* xu = (float*)(pb + L.xu);
-  int* cum = (int*)(pb + L.cum);
-  double* pxd = (double*)(pb + L.pxd);
-  if (t < Ne) xl[t] = x[(size_t)b * Ne + t];
-  for (int w = t; w < Ne * WE; w += 256) al[w] = abits[(size_t)b * Ne * WE + w];
-  __syncthreads();
-  if (t < Ne) al[t * WE + (t >> 5)] &= ~(1u << (t & 31));      // a_ii is not a relation
-  __syncthreads();
-  if (t < Ne) {
-    const float xi = xl[t];
-    int r = 0;
-    for (int j = 0; j < Ne; ++j) {
-      const float xj = xl[j];
-      r += (xj < xi || (xj == xi && j < t)) ? 1 : 0;
-    }
-    xsl[r] = xi;
-    xsrt[r] = xi;
-    perm[r] = t;
-  }
-  __shared__ uint32_t atl[256 * 8];
-  __shared__ int offl[2][260];
-  for (int e = t; e < Ne * WE; e += 256) {          // a^T bits
-    const int j = e / WE, w = e - j * WE;
-    uint32_t bits = 0;
-    for (int l = 0; l < 32; ++l) {
-      const int i = 32 * w + l;
-      if (i < Ne) bits |= ((al[i * WE + (j >> 5)] >> (j & 31)) & 1u) << l;
-    }
-    atl[e] = bits;
-  }
-  __syncthreads();
-  __shared__ int xof[2][260];
-  if (t < Ne) {
-    int dr = 0, dc = 0;
-    for (int w = 0; w < WE; ++w) {
-      dr += __builtin_popcount(al[t * WE + w]);
-      dc += __builtin_popcount(atl[t * WE + w]);
-    }
-    offl[0][t] = dr;
-    offl[1][t] = dc;
-    xof[0][t] = (dr + 3) & ~3;
-    xof[1][t] = (dc + 3) & ~3;
-  }
-  __syncthreads();
-  if (t == 0) {            // serial scans of the padded x-list lengths, rows then columns
-    int acc = 0;
-    for (int s2 = 0; s2 < 2; ++s2) {
-      int* dst = (int*)(pb + (s2 ? L.xoffc : L.xoffr));
-      for (int i = 0; i < Ne; ++i) {
-        const int d = xof[s2][i];
-        xof[s2][i] = acc;
-        dst[i] = acc;
-        acc += d;
-      }
-      xof[s2][Ne] = acc;
-      dst[Ne] = acc;
-    }
-  }
-  if (t < 2) {                                       // serial exclusive scans, once per batch
-    int acc = 0;
-    for (int i = 0; i < Ne; ++i) {
-      const int d = offl[t][i];
-      offl[t][i] = acc;
-      ((int*)(pb + (t ? L.offc : L.offr)))[i] = acc;
-      acc += d;
-    }
-    offl[t][Ne] = acc;
-    ((int*)(pb + (t ? L.offc : L.offr)))[Ne] = acc;
-  }
-  __syncthreads();
-  const int cbase = (offl[0][Ne] + 3) & ~3;
-  if (t == 0) {
-    pb[L.meta + 1] = (uint32_t)offl[0][Ne];
-    pb[L.meta + 2] = (uint32_t)offl[1][Ne];
-    pb[L.meta + 3] = (uint32_t)cbase;
-  }
-  if (t < Ne) {
-    uint8_t* lb = reinterpret_cast<uint8_t*>(pb + L.lists);
-    float* xlp = reinterpret_cast<float*>(pb + L.xl);
-    int xr = xof[0][t], xc = xof[1][t];
-    for (int w = 0; w < WE; ++w) {
-      uint32_t m = al[t * WE + w];
-      while (m) {
-        const int j = 32 * w + __builtin_ctz(m);
-        lb[xr] = (uint8_t)j;
-        xlp[xr++] = xl[j];
-        m &= m - 1u;
-      }
-      m = atl[t * WE + w];
-      while (m) {
-        xlp[xc++] = xl[32 * w + __builtin_ctz(m)];
-        m &= m - 1u;
-      }
-    }
-    const float qnan = __builtin_nanf("");      // clamp_fma2(NaN) = 0: pads add nothing
-    for (; xr < xof[0][t + 1]; ++xr) { xlp[xr] = qnan; lb[xr] = 0; }
-    for (; xc < xof[1][t + 1]; ++xc) xlp[xc] = qnan;
-  }
-  __syncthreads();
-  if (t == 0) {   // serial over <= 256 sorted values, once per batch
-    int nd = 0;
-    double s = 0.0;
-    for (int m = 0; m < Ne; ++m) {
-      const float v = xsl[m];
-      if (m == 0 || v != xsl[m - 1]) {
-        xu[nd] = v;
-        cum[nd] = m;
-        pxd[nd] = s;
-        ++nd;
-      }
-      s += (double)v;
-    }
-    cum[nd] = Ne;
-    pxd[nd] = s;
-    pb[L.meta] = (uint32_t)nd;
-  }
-}
-
-// Cross-graph aggregation counts.  marshalling_B2 (model_2.py:146-150, dense maps of
-// utils2.py:111-137) is n_c = sum_r ([s_r = c] + [t_r = c]) B2_r with
-// B2_r = [x'_I, x'_J, [a_IJ = 0], [a_IJ = 1]], (I, J) = relation r on the Ne-grid and
-// s_r = hid[i'], t_r = hid[j'] with (i', j') = relation r on the n-grid (r < n(n-1)).
-// Only x' changes between steps, so
-//   n_c[0] = sum_I ks[c][I] x'_I,  n_c[1] = sum_J kt[c][J] x'_J,  n_c[2:4] = ncst[c]
-// ks[c][I] = #{r in Ne-row I : s_r = c} + #{r in Ne-row I : t_r = c}, kt over Ne-columns.
-//
-// k_prep_counts grid (ceil(Ne / TI), B, 2): block (tile, b, z) owns TI Ne-rows (z = 0: ks,
-// plus the class counts) or TI Ne-columns (z = 1: kt) of commit b and visits each of their
-// relations once, counting into an LDS histogram [Nc][TI] (integer, order-independent).
-// Lanes hold consecutive relations of a row (or column), whose hunk ids repeat in runs
-// (s_r is constant over n-1 consecutive relations): each run of equal counter addresses in
-// consecutive lanes is one LDS atomic by its first lane (ballot masks), not a same-address
-// conflict per lane.  The tile's counters are written as coalesced u16 rows; the class
-// counts are summed over tiles with global u32 atomics into ncst (zeroed, then converted to
-// f32 in place by k_prep_ncst).  The count arrays live at word offsets (o_ks, o_kt, o_ncst)
-// of each commit's prep block of `stride` words (fused layout: prep_layout; general path:
-// its own layout).
-// ------------------------------------------------------------------------------
-__device__ __forceinline__ void divmod_exact(int r, int d, float inv, int& q, int& rem) {
-  q = (int)((float)r * inv);
-  rem = r - q * d;
-  while (rem < 0) { --q; rem += d; }
-  while (rem >= d) { ++q; rem -= d; }
-}
-
-// counter[key] += (number of consecutive valid lanes from this lane with the same key),
-// issued by the first lane of each run; invalid lanes end runs.  All 64 lanes take part.
-__device__ __forceinline__ void run_add(uint32_t* counter, int key, bool valid, int lane) {
-  const int kp = __shfl_up(key, 1, 64);
-  const unsigned long long V = __ballot(valid);
-  const bool pv = lane > 0 && ((V >> (lane - 1)) & 1ull);   // previous lane in a run
-  const bool lead = valid && (!pv || kp != key);
-  const unsigned long long L = __ballot(lead);
-  if (lead) {
-    const unsigned long long stop =
-        (L | ~V) & (lane == 63 ? 0ull : (~0ull << (lane + 1)));
-    const int nxt = stop ? __builtin_ctzll(stop) : 64;
-    atomicAdd(&counter[key], (uint32_t)(nxt - lane));
-  }
-}
-
-__global__ __launch_bounds__(512) void k_prep_counts(const uint32_t* __restrict__ abits,
-                                                     const int32_t* __restrict__ hidg,
-                                                     const int32_t* __restrict__ nleng,
-                                                     uint32_t* __restrict__ prep, int Ne, int Nc,
-                                                     int TI, int stride, int o_ks, int o_kt,
-                                                     int o_ncst) {
-  extern __shared__ uint32_t hist[];   // [Nc][TI + 1] | class counts [Nc][2] | hid [Ne] |
-                                       // the tile's a-rows [TI][WE] (z = 0)
-  const int z = blockIdx.z, b = blockIdx.y, L0 = blockIdx.x * TI, t = threadIdx.x;
-  const int lane = t & 63;
-  const int WE = (Ne + 31) >> 5;
-  uint32_t* pb = prep + (size_t)b * stride;
-  const int TP = TI + 1;               // odd row stride: the hunks of one row / column of the
-                                       // tile fall in different LDS banks
-  uint32_t* ncl = hist + Nc * TP;
-  int32_t* hid = reinterpret_cast<int32_t*>(ncl + 2 * Nc);   // LDS copies: the per-relation
-  uint32_t* ab = ncl + 2 * Nc + Ne;                          // lookups stay on-chip
-  int n = nleng[b];
-  n = n < 0 ? 0 : (n > Ne ? Ne : n);
-  const int nrel = n >= 2 ? n * (n - 1) : 0;
-  const int n1 = n >= 2 ? n - 1 : 1, Ne1 = Ne - 1;
-  const float invn = 1.f / (float)n1, invE = 1.f / (float)(Ne1 > 0 ? Ne1 : 1);
-  const int nl = Ne - L0 < TI ? Ne - L0 : TI;
-  for (int e = t; e < Ne; e += 512) hid[e] = hidg[(size_t)b * Ne + e];
-  if (z == 0)
-    for (int e = t; e < nl * WE; e += 512) ab[e] = abits[((size_t)b * Ne + L0) * WE + e];
-  for (int e = t; e < Nc * TP + 2 * Nc; e += 512) hist[e] = 0;
-  __syncthreads();
-  const int items = nl * Ne1;
-  for (int e0 = 0; e0 < items; e0 += 512) {   // block-uniform trips: every lane takes part
-    const int e = e0 + t;
-    int li = 0, k = 0, I = 0, jj = 0, J = 0;
-    if (e < items) divmod_exact(e, Ne1, invE, li, k);
-    if (z == 0) { I = L0 + li; jj = k; J = jj + (jj >= I ? 1 : 0); }
-    else { J = L0 + li; I = k + (k >= J ? 1 : 0); jj = J - (J > I ? 1 : 0); }
-    const int r = I * Ne1 + jj;
-    const bool in = e < items && r < nrel;
-    int hs = -1, ht = -1, a = 0;
-    if (in) {
-      int ip, jjp;
-      divmod_exact(r, n1, invn, ip, jjp);
-      const int jp = jjp + (jjp >= ip ? 1 : 0);
-      hs = hid[ip];
-      ht = hid[jp];
-      if (z == 0) a = (int)((ab[li * WE + (J >> 5)] >> (J & 31)) & 1u);
-    }
-    const bool vs = hs >= 0 && hs < Nc, vt = ht >= 0 && ht < Nc;
-    run_add(hist, vs ? hs * TP + li : 0, vs, lane);
-    run_add(hist, vt ? ht * TP + li : 0, vt, lane);
-    if (z == 0) {
-      run_add(ncl, vs ? 2 * hs + a : 0, vs, lane);
-      run_add(ncl, vt ? 2 * ht + a : 0, vt, lane);
-    }
-  }
-  __syncthreads();
-  uint16_t* out = (uint16_t*)(pb + (z ? o_kt : o_ks));
-  for (int e = t; e < Nc * TI; e += 512) {
-    const int c = e / TI, i = e - c * TI;
-    if (i < nl) out[(size_t)c * Ne + L0 + i] = (uint16_t)hist[c * TP + i];
-  }
-  if (z == 0) {
-    uint32_t* nc = pb + o_ncst;
-    for (int e = t; e < 2 * Nc; e += 512)
-      if (ncl[e]) atomicAdd(&nc[e], ncl[e]);
-  }
-}
-
-// Upload-time marshalling (hdg_pack_classes): (B, N, N) u8 class grid -> (B, N, ceil(N/32))
-// u32 rows, bit j of row i = (class(i, j) == 1), diagonal cleared -- the E_edge / C_edge
-// one-hots of utils2.py:82, 105 as hdg_batch's abits / ybits.  One thread per word.
-__global__ __launch_bounds__(256) void k_pack_classes(const uint8_t* __restrict__ cls, const int N,
-                                                      const int W, const long long words,
-                                                      uint32_t* __restrict__ bits) {
-  const long long w = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (w >= words) return;
-  const long long row = w / W;
-  const int wi = (int)(w - row * W), i = (int)(row % N), j0 = 32 * wi;
-  const uint8_t* src = cls + row * N + j0;
-  const int n = N - j0 < 32 ? N - j0 : 32;
-  uint32_t b = 0u;
-  for (int l = 0; l < n; ++l) b |= (src[l] == 1 ? 1u : 0u) << l;
-  if (i >= j0 && i < j0 + 32) b &= ~(1u << (i - j0));   // a_ii is not a relation
-  bits[w] = b;
-}
-
-// grid (B): mode 0 zeroes the class-count words of each commit, mode 1 turns the summed
-// u32 counts into the f32 values the step kernels read (exact: counts < 2^24)
-__global__ __launch_bounds__(256) void k_prep_ncst(uint32_t* __restrict__ prep, int Nc,
-                                                   int stride, int o_ncst, int mode) {
-  uint32_t* nc = prep + (size_t)blockIdx.x * stride + o_ncst;
-  for (int e = threadIdx.x; e < 2 * Nc; e += 256) {
-    if (mode == 0) nc[e] = 0u;
-    else nc[e] = __float_as_uint((float)nc[e]);
-  }
-}
-
 // ------------------------------------------------------------------------------
 // k_commit_step: the whole per-commit forward + backward, one 1024-thread block per
 // commit.  Node arrays live in LDS; one union region U is re-carved per phase
@@ -1275,9 +898,6 @@ __host__ __device__ inline StepLayout step_layout(int Ne, int Nc, int smaxc) {
   L.total = o;
   return L;
 }
-
-using hdg::f4v;
-using hdg::mfma_tile16_p;
 
 // One 16x16 tile of C = A.B on v_mfma_f32_16x16x4_f32 (f32 in, f32 accumulate; exact
 // f32 fmaf-chain numerics).  fa(r, k) = A[row0 + r][k], fb(k, c) = B[k][col0 + c], both
@@ -1439,7 +1059,7 @@ __device__ __forceinline__ void entity_fwd(const int t, const float* Ws,
         const float nr = (float)(cum[rhi] - cum[rlo]), nc = (float)(cum[chi] - cum[clo]);
         float acc = fmaf(nr, u[h], w1[h] * sxr);
         acc += fmaf(nc, v[h] + c0[h], w0[h] * sxc);
-        tot[h] = fmaf(-2.f, reluf(u[h] + v[h]), acc);
+        tot[h] = fmaf(-2.f, relu(u[h] + v[h]), acc);
       }
     }
     // a = 1 corrections relu(z0 + d) - relu(z0) = d clamp((s z0 + t) / d, 0, 1) with
@@ -1643,9 +1263,6 @@ typedef uint32_t xu4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void xstore(xu4* p, const xu4 w) {
   asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(w) : "memory");
-}
-__device__ __forceinline__ void xstore1(uint32_t* p, const uint32_t w) {
-  asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(w) : "memory");
 }
 __device__ __forceinline__ xu4 xload(const xu4* p) {
   xu4 w;
@@ -2030,7 +1647,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
           for (int q = 0; q < 4; ++q) {
             const int i = row0 + 4 * (lane >> 4) + q;
             const bool own = i >= nlo && i < nhi;
-            const float v = reluf(fmaf(xs[own ? i : nlo], w0, c[q]) + bias);
+            const float v = relu(fmaf(xs[own ? i : nlo], w0, c[q]) + bias);
             if (own) hEG[i * HS + m] = v;
             ow[q] = fmaf(v, w2, ow[q]);
           }
@@ -2041,7 +1658,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
       if (q < 4 && i >= nlo && i < nhi) {
         const float o = (q == 0 ? ow[0] : q == 1 ? ow[1] : q == 2 ? ow[2] : ow[3]) + Ws[E3_B2];
         os[i] = o;
-        xps[i] = reluf(o);
+        xps[i] = relu(o);
       }
     }
   }
@@ -2191,7 +1808,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     auto m5fix = [&](int j, int kk, float v) {
       const int e = j * HS + kk;
       if (!SPLIT || (j & 1) == h) {
-        const float dg = reluf(alpha[e] + beta[e]);
+        const float dg = relu(alpha[e] + beta[e]);
         G[e] -= dg;
         v -= dg;
       }
@@ -2306,10 +1923,10 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
           c.z = fmaf(ey, ee.z, c.z);
           c.w = fmaf(ey, ee.w, c.w);
         }
-        kap[4 * v] = reluf(a.x + c.x);
-        kap[4 * v + 1] = reluf(a.y + c.y);
-        kap[4 * v + 2] = reluf(a.z + c.z);
-        kap[4 * v + 3] = reluf(a.w + c.w);
+        kap[4 * v] = relu(a.x + c.x);
+        kap[4 * v + 1] = relu(a.y + c.y);
+        kap[4 * v + 2] = relu(a.z + c.z);
+        kap[4 * v + 3] = relu(a.w + c.w);
         const float4 cw = cv4[v];
         da = fmaf(kap[4 * v], cw.x, da);
         dbb = fmaf(kap[4 * v + 1], cw.y, dbb);
@@ -2342,7 +1959,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
       const float inv = __builtin_amdgcn_rcpf(1.f + ex);   // 1 + e in (1, 2]: 1-ulp rcp
       const float pbig = inv, psmall = ex * inv;
       const float p1 = d >= 0.f ? pbig : psmall, p0 = d >= 0.f ? psmall : pbig;
-      ce_acc += ln_1to2(1.f + ex) + reluf(yf > 0.f ? -d : d);
+      ce_acc += ln_1to2(1.f + ex) + relu(yf > 0.f ? -d : d);
       corr += ((p1 > p0) == (yf > 0.f)) ? 1.f : 0.f;   // top_ACC: np.argmax, ties -> 0
       if (prb) { prb[e] = p0; prb[Pc + e] = p1; }
       if constexpr (TRAIN) {
@@ -2948,69 +2565,6 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
 #undef WAVE_STAMP
 }
 
-// ------------------------------------------------------------------------------
-// deterministic reduction of the partial rows (one per block of k_commit_step): a
-// 1024-thread block takes RED_P = 16 parameters x 64 row phases (row r -> phase r % 64,
-// fixed order); a thread's <= 4 rows per trip are loaded before they are added (one
-// memory round trip up to 256 rows), the 4 phases of a wave close with two permlane
-// swaps, the 16 waves in a fixed-order LDS sum.  Bitwise reproducible.  The correct-
-// prediction count (slot NP + HDG_TR_COUNT, an exact integer per row) is summed as an
-// integer alongside and returned in `count` (thread pl of that slot's block).
-// ------------------------------------------------------------------------------
-constexpr int RED_P = 16, RED_PH = NT_MID / RED_P;   // 16 parameters x 64 phases
-constexpr int CNT_SLOT = m2::NP + HDG_TR_COUNT;
-
-struct RedShared {
-  float s[NT_MID / 64][RED_P];
-  uint32_t c[NT_MID / 16];             // per (wave, phase lane group) count partials
-};
-
-__device__ __forceinline__ float reduce_commits(const float* __restrict__ part, int R, int p,
-                                                bool valid, RedShared& sh, uint32_t& count) {
-  const int pl = threadIdx.x & (RED_P - 1), ph = threadIdx.x / RED_P;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const bool isc = p == CNT_SLOT;
-  float acc = 0.f;
-  uint32_t accu = 0u;
-  if (valid) {
-    for (int b0 = ph; b0 < R; b0 += 4 * RED_PH) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int b = b0 + u * RED_PH;
-        v[u] = b < R ? part[(size_t)b * NPART + p] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc += v[u];
-      if (isc) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) accu += (uint32_t)v[u];
-      }
-    }
-  }
-  acc = xrow_sum4(acc);                 // the wave's 4 phases (lanes pl, pl+16, +32, +48)
-  if (lane < RED_P) sh.s[wv][pl] = acc;
-  if (isc) sh.c[wv * 4 + (lane >> 4)] = accu;
-  __syncthreads();
-  float g = 0.f;
-  count = 0u;
-  if (threadIdx.x < RED_P) {
-#pragma unroll
-    for (int q = 0; q < NT_MID / 64; ++q) g += sh.s[q][pl];
-    if (isc)
-      for (int q = 0; q < NT_MID / 16; ++q) count += sh.c[q];
-  }
-  return g;
-}
-
-// the trailer's count slots from the integer total (each part < 2^16: exact under any
-// float all-reduce of up to 256 ranks)
-__device__ __forceinline__ void put_count(float* __restrict__ out, const uint32_t c) {
-  out[0] = (float)(c & 0xFFFFu);
-  out[1] = (float)(c >> 16);
-  out[2] = 0.f;
-}
-
 // slots [p_begin, p_end) -> out[p - p_begin], those >= shift_at moved by shift (model_4 on
 // the fused path: the model_2-layout slots past the entity-edge block)
 __global__ __launch_bounds__(1024) void k_grad_reduce(const float* __restrict__ part, int B,
@@ -3092,8 +2646,6 @@ __global__ __launch_bounds__(1024) void k_reduce_adam(const float* __restrict__ 
 //   lr_t = lr sqrt(1-b2^t)/(1-b1^t);  m += (g-m)(1-b1); v += (g^2-v)(1-b2);
 //   var -= lr_t m / (sqrt(v) + eps)     (tensorflow/core/kernels/training_ops.cc ApplyAdam)
 // ------------------------------------------------------------------------------
-constexpr int ADAM_PT = 4;   // parameters per thread: 4 x 1024 >= every variant's count
-
 __global__ __launch_bounds__(1024) void k_adam_tf(float* __restrict__ params,
                                                   float* __restrict__ mm,
                                                   float* __restrict__ vv,
@@ -3171,313 +2723,6 @@ __global__ __launch_bounds__(1024) void k_adam_tf(float* __restrict__ params,
 }
 
 // ------------------------------------------------------------------------------
-// Data-parallel tail over xGMI (include/hdgnn.h hdg_*_dp).
-// Every rank owns a mailbox of uncached device memory that each peer maps through HIP
-// IPC.  Block k of the tail kernel owns gradient slots [16k, 16k + 16): it forms its
-// local values (the fixed-order sum of the partial rows, or the rank's reduced gradient),
-// writes each as an 8-byte (value, tag) word with a system-scope write-through store into
-// slot (parity, rank, p) of EVERY peer's mailbox (xGMI, one hop, all peers at once; the
-// 8-byte word is single-copy atomic, as in RCCL's LL protocol), polls its own mailbox for
-// the peers' words with L2-bypassing loads, and sums the world's values in rank order
-// 0..W-1: every rank holds the same bits, so the replicas stay bitwise equal.
-//   tag = epoch << 1 | fault: epoch is a per-block launch counter kept in the own mailbox
-//   (all ranks issue the same launches); parity = epoch & 1 double-buffers the words, so
-//   a rank one launch ahead writes over words every peer has already read (it needed the
-//   peers' words of its previous launch, which they sent after reading theirs).  A peer
-//   that never arrives ends the wait after wait_ticks: HDG_STATUS_DP_TIMEOUT, NaN loss,
-//   no update on that block -- never a hang.
-// ------------------------------------------------------------------------------
-namespace dpk {
-constexpr int MAXW = HDG_DP_MAX_WORLD;
-constexpr int GLENP = HDG_DP_MAX_LEN;               // >= every variant's grad length, x16
-constexpr int NBLK = GLENP / RED_P;
-constexpr size_t DATA_WORDS = 2ull * MAXW * GLENP;  // u64 (value, tag) words
-constexpr size_t OFF_EPOCH = DATA_WORDS * 8;        // u32 [256] per-block launch counters
-constexpr size_t OFF_AUX = OFF_EPOCH + 256 * 4;     // f32 [8] loss terms + Adam factor
-constexpr size_t OFF_GLOC = OFF_AUX + 8 * 4;        // f32 [GLENP] the rank's own gradient
-constexpr size_t BYTES = OFF_GLOC + GLENP * 4;      //   (general path, hdg_train_step_dp)
-constexpr unsigned long long WAIT_DEFAULT = 1000000000ull;   // 10 s of s_memrealtime
-static_assert(GLENP % RED_P == 0 && NBLK <= 256, "mailbox layout");
-static_assert(GLENP >= 3129 + HDG_TRAILER, "every variant's gradient fits a mailbox row");
-enum { SUM = 0, PART = 1, GRAD = 2 };
-}  // namespace dpk
-// SUM / GRAD blocks only move 16 words per rank: 256 threads (16 ranks x 16 slots), so
-// the grid stays small and resident even when several ranks share one device (tests);
-// PART runs k_reduce_adam's 1024-thread reduction first
-constexpr int DP_NT_LIGHT = dpk::MAXW * RED_P;
-
-struct DpArgs {
-  uint32_t* box[dpk::MAXW];
-  int rank, world;
-  unsigned long long wait;
-};
-
-typedef uint32_t xu2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void dstore2(uint32_t* p, const xu2 w) {
-  asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(w) : "memory");
-}
-__device__ __forceinline__ xu2 dload2(const uint32_t* p) {
-  xu2 w;
-  asm volatile("global_load_dwordx2 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)"
-               : "=v"(w) : "v"(p) : "memory");
-  return w;
-}
-__device__ __forceinline__ uint32_t* dp_slot(uint32_t* box, uint32_t par, int src, int p) {
-  return box + 2 * (((size_t)par * dpk::MAXW + src) * dpk::GLENP + p);
-}
-
-// MODE SUM:  gout = world sum of src[0..glen)                       (hdg_dp_allreduce)
-// MODE PART: local = fixed-order sum of R partial rows (k_reduce_adam's reduction), then
-//            world sum -> gout, TF Adam with aux from k_commit_step   (hdg_train_step_dp)
-// MODE GRAD: local = src[0..glen) (a rank's reduced gradient), aux from k_dp_aux (hdg_adam_dp)
-template <int MODE>
-__global__ __launch_bounds__(1024) void k_dp_tail(const float* __restrict__ src, const int R,
-                                                  const int np, const int glen,
-                                                  float* __restrict__ gout,
-                                                  float* __restrict__ params,
-                                                  float* __restrict__ mm, float* __restrict__ vv,
-                                                  float* __restrict__ bpow,
-                                                  const float* __restrict__ aux, const float lr,
-                                                  const float inv_pairs,
-                                                  float* __restrict__ stats,
-                                                  uint32_t* __restrict__ status,
-                                                  const int fault_rows, const DpArgs d) {
-  __shared__ RedShared sh;
-  __shared__ float gl[RED_P];
-  __shared__ float vals[dpk::MAXW][RED_P];
-  __shared__ uint32_t s_ep, s_cnt;
-  const int t = threadIdx.x, blk = blockIdx.x;
-  const int l = t & (RED_P - 1), r = t / RED_P;
-  const int p = blk * RED_P + l;
-  uint32_t* own = d.box[d.rank];
-  uint32_t* ep = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(own) + dpk::OFF_EPOCH);
-  if (t == 0) s_ep = ep[blk] + 1u;
-  // the update's operands are fetched first so their latency overlaps the reduction
-  bool upd = MODE != dpk::SUM && t < RED_P && p < np;
-  const float w = upd ? params[p] : 0.f, m0 = upd ? mm[p] : 0.f, v0 = upd ? vv[p] : 0.f;
-  float g = 0.f;
-  bool bad = false;
-  if constexpr (MODE == dpk::PART) {
-    for (int q = t; q < fault_rows; q += 1024)             // k_commit_step's fsl
-      bad |= src[(size_t)fault_rows * NPART + q] != 0.f;
-    uint32_t cnt;
-    g = reduce_commits(src, R, p, p < glen, sh, cnt);
-    if (t < RED_P && p == CNT_SLOT) s_cnt = cnt;
-  } else {
-    if (t < RED_P && p < glen) g = src[p];
-    if constexpr (MODE == dpk::GRAD) bad = t == 0 && src[np + HDG_TR_FAULT] != 0.f;
-  }
-  bad = __syncthreads_or(bad);               // also publishes s_ep and s_cnt
-  if (t < RED_P) {
-    if (MODE == dpk::PART && p >= CNT_SLOT && p <= CNT_SLOT + 2)   // three 16-bit parts
-      g = p == CNT_SLOT ? (float)(s_cnt & 0xFFFFu) : (p == CNT_SLOT + 1 ? (float)(s_cnt >> 16) : 0.f);
-    gl[l] = g;
-  }
-  __syncthreads();
-  const uint32_t e = s_ep, par = e & 1u;
-  const bool mine = r < d.world && p < glen;
-  if (mine && r != d.rank)                    // to every peer at once
-    dstore2(dp_slot(d.box[r], par, d.rank, p),
-            (xu2){__float_as_uint(gl[l]), (e << 1) | (bad ? 1u : 0u)});
-  bool late = false, rbad = false;
-  if (mine) {
-    float v = gl[l];
-    if (r != d.rank) {
-      const uint32_t* in = dp_slot(own, par, r, p);
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      xu2 wd = dload2(in);
-      while ((wd.y >> 1) != (e & 0x7FFFFFFFu)) {
-        if (__builtin_amdgcn_s_memrealtime() - t0 > d.wait) { late = true; break; }
-        __builtin_amdgcn_s_sleep(1);
-        wd = dload2(in);
-      }
-      v = __uint_as_float(wd.x);
-      rbad = (wd.y & 1u) != 0u;
-    }
-    vals[r][l] = v;
-  }
-  const bool anylate = __syncthreads_or(late);
-  const bool anybad = __syncthreads_or(rbad) || bad;
-  if (t == 0) ep[blk] = e;                    // this block's launch is consumed
-  if (t >= RED_P || p >= glen) return;
-  float tot = 0.f;
-  for (int q = 0; q < d.world; ++q) tot += vals[q][l];
-  if (MODE != dpk::SUM && p == np + HDG_TR_CE && anylate) tot = __builtin_nanf("");
-  gout[p] = tot;
-  if (anylate && t == 0 && status) xstore1(status, HDG_STATUS_DP_TIMEOUT);
-  if constexpr (MODE == dpk::SUM) return;
-  const int TH1 = np - 4, TH2 = np - 2;
-  if (stats && p >= np + HDG_TR_COUNT && p <= np + HDG_TR_FAULT)   // count parts, fault
-    stats[4 + (p - np - HDG_TR_COUNT)] = tot;
-  if (p == np + HDG_TR_CE && stats) {
-    const float ce = tot * inv_pairs;
-    stats[0] = ce;
-    stats[1] = aux[1];
-    stats[2] = aux[0];
-    stats[3] = 10.f * ce + 0.1f * aux[1] + aux[0];
-  }
-  if (anylate || anybad) upd = false;
-  if (upd) {
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    const float lr_t = lr * aux[4], n1 = aux[2], n2 = aux[3];
-    float gg = tot + 0.001f * w;
-    if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w / n1;
-    if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w / n2;
-    float m = m0, v = v0;
-    m += (gg - m) * (1.f - b1);
-    v += (gg * gg - v) * (1.f - b2);
-    mm[p] = m;
-    vv[p] = v;
-    params[p] = w - lr_t * m / (sqrtf(v) + eps);
-  }
-  if (blk == 0 && t == 0 && upd) {
-    bpow[0] = aux[5];
-    bpow[1] = aux[6];
-  }
-}
-
-// k_dp_tail's SUM / GRAD modes for ranks that share a device (hdg_dp.flags HDG_DP_SHARED):
-// G blocks per rank (dp_shared_grid: (W - 1) G <= CUs / 2, G >= HDG_DP_SHARED_BLOCKS),
-// block b owning the slot groups b, b + G, ... .  A
-// block first sends the words of all its groups (the values are src[p], the epoch of group
-// k is ep[k] + 1 as in k_dp_tail), then receives, sums and updates its groups in order:
-// the same words, tags, rank-order sums and Adam arithmetic as one k_dp_tail block per
-// group, so the two kernels give the same bits and keep the same per-group launch counters.
-// Only G blocks per rank spin, so the W-1 ranks waiting for the last one cover at most
-// half the CUs and the last rank's step kernel always finds CUs to run on.
-template <int MODE>
-__global__ __launch_bounds__(DP_NT_LIGHT) void k_dp_tail_shared(
-    const float* __restrict__ src, const int np, const int glen, float* __restrict__ gout,
-    float* __restrict__ params, float* __restrict__ mm, float* __restrict__ vv,
-    float* __restrict__ bpow, const float* __restrict__ aux, const float lr,
-    const float inv_pairs, float* __restrict__ stats, uint32_t* __restrict__ status,
-    const DpArgs d) {
-  static_assert(MODE != dpk::PART, "the shared-device tail exchanges a reduced gradient");
-  __shared__ float vals[dpk::MAXW][RED_P];
-  const int t = threadIdx.x, l = t & (RED_P - 1), r = t / RED_P;
-  const int ngrp = (glen + RED_P - 1) / RED_P;
-  uint32_t* own = d.box[d.rank];
-  uint32_t* ep = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(own) + dpk::OFF_EPOCH);
-  const bool bad = MODE == dpk::GRAD && src[np + HDG_TR_FAULT] != 0.f;
-  // 1. every word of this block's groups to every peer
-  if (r < d.world && r != d.rank) {
-    for (int k = blockIdx.x; k < ngrp; k += gridDim.x) {
-      const int p = k * RED_P + l;
-      const uint32_t e = ep[k] + 1u;
-      if (p < glen)
-        dstore2(dp_slot(d.box[r], e & 1u, d.rank, p),
-                (xu2){__float_as_uint(src[p]), (e << 1) | (bad ? 1u : 0u)});
-    }
-  }
-  // 2. per group: the peers' words, the rank-order sum, TF Adam
-  for (int k = blockIdx.x; k < ngrp; k += gridDim.x) {
-    const int p = k * RED_P + l;
-    const uint32_t e = ep[k] + 1u, par = e & 1u;
-    bool upd = MODE != dpk::SUM && t < RED_P && p < np;
-    const float w = upd ? params[p] : 0.f, m0 = upd ? mm[p] : 0.f, v0 = upd ? vv[p] : 0.f;
-    bool late = false, rbad = false;
-    if (r < d.world && p < glen) {
-      float v;
-      if (r != d.rank) {
-        const uint32_t* in = dp_slot(own, par, r, p);
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        xu2 wd = dload2(in);
-        while ((wd.y >> 1) != (e & 0x7FFFFFFFu)) {
-          if (__builtin_amdgcn_s_memrealtime() - t0 > d.wait) { late = true; break; }
-          __builtin_amdgcn_s_sleep(1);
-          wd = dload2(in);
-        }
-        v = __uint_as_float(wd.x);
-        rbad = (wd.y & 1u) != 0u;
-      } else {
-        v = src[p];
-      }
-      vals[r][l] = v;
-    }
-    const bool anylate = __syncthreads_or(late);
-    const bool anybad = __syncthreads_or(rbad) || bad;
-    if (t == 0) ep[k] = e;                      // this group's launch is consumed
-    if (t < RED_P && p < glen) {
-      float tot = 0.f;
-      for (int q = 0; q < d.world; ++q) tot += vals[q][l];
-      if (MODE != dpk::SUM && p == np + HDG_TR_CE && anylate) tot = __builtin_nanf("");
-      gout[p] = tot;
-      if (anylate && t == 0 && status) xstore1(status, HDG_STATUS_DP_TIMEOUT);
-      if constexpr (MODE == dpk::GRAD) {
-        const int TH1 = np - 4, TH2 = np - 2;
-        if (stats && p >= np + HDG_TR_COUNT && p <= np + HDG_TR_FAULT)
-          stats[4 + (p - np - HDG_TR_COUNT)] = tot;
-        if (p == np + HDG_TR_CE && stats) {
-          const float ce = tot * inv_pairs;
-          stats[0] = ce;
-          stats[1] = aux[1];
-          stats[2] = aux[0];
-          stats[3] = 10.f * ce + 0.1f * aux[1] + aux[0];
-        }
-        if (anylate || anybad) upd = false;
-        if (upd) {
-          const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-          const float lr_t = lr * aux[4], n1 = aux[2], n2 = aux[3];
-          float gg = tot + 0.001f * w;
-          if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w / n1;
-          if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w / n2;
-          float m = m0, v = v0;
-          m += (gg - m) * (1.f - b1);
-          v += (gg * gg - v) * (1.f - b2);
-          mm[p] = m;
-          vv[p] = v;
-          params[p] = w - lr_t * m / (sqrtf(v) + eps);
-        }
-        if (k == 0 && t == 0 && upd) {
-          bpow[0] = aux[5];
-          bpow[1] = aux[6];
-        }
-      }
-    }
-    __syncthreads();                            // vals is rewritten by the next group
-  }
-}
-
-// aux for MODE GRAD (k_commit_step's block 0 writes it on the fused path): loss terms of
-// the pre-update parameters (model_2.py:123-130, 326-333) and TF ApplyAdam's lr factor,
-// in k_adam_tf's summation order
-__global__ __launch_bounds__(1024) void k_dp_aux(const float* __restrict__ params, const int np,
-                                                 const float* __restrict__ bpow,
-                                                 float* __restrict__ aux) {
-  const int TH1 = np - 4, TH2 = np - 2;
-  __shared__ float red[16 * 4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  float l2 = 0.f, t1 = 0.f, t2 = 0.f;
-#pragma unroll
-  for (int u = 0; u < ADAM_PT; ++u) {
-    const int p = t + u * 1024;
-    const float w = p < np ? params[p] : 0.f;
-    l2 = fmaf(w, w, l2);
-    if (p >= TH1 && p < TH1 + 2) t1 = fmaf(w, w, t1);
-    if (p >= TH2 && p < TH2 + 2) t2 = fmaf(w, w, t2);
-  }
-  l2 = wave_sum(l2);
-  t1 = wave_sum(t1);
-  t2 = wave_sum(t2);
-  if (lane == 0) { red[wv * 4] = l2; red[wv * 4 + 1] = t1; red[wv * 4 + 2] = t2; }
-  __syncthreads();
-  if (t == 0) {
-    float s[3] = {0.f, 0.f, 0.f};
-    for (int q = 0; q < 16; ++q)
-      for (int c = 0; c < 3; ++c) s[c] += red[q * 4 + c];
-    const float n1 = sqrtf(s[1]), n2 = sqrtf(s[2]);
-    const float b1p = bpow[0], b2p = bpow[1];
-    aux[0] = 0.0005f * s[0];
-    aux[1] = 0.01f * (n2 + n1);
-    aux[2] = n1;
-    aux[3] = n2;
-    aux[4] = sqrtf(1.f - b2p) / (1.f - b1p);
-    aux[5] = b1p * 0.9f;
-    aux[6] = b2p * 0.999f;
-  }
-}
-
-// ------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------
 int smax_c(int nc) { return nc <= 80 ? 5 : (nc <= 128 ? 8 : 10); }
@@ -3503,18 +2748,6 @@ Work work_layout(const hdg_shape* s) {
   w.xch = take(2 * B * 4 * ((size_t)XSLOTS * NC16 * HS / 2 + XRHO) + B);   // + epochs
   w.total = o;
   return w;
-}
-
-// k_prep_counts tile width: TI Ne-rows / -columns per block (<= 64 KiB of counters where
-// possible, two blocks per CU), and the LDS words it needs
-int prep_lds_words(int ne, int nc, int ti) {
-  return (ti + 1) * nc + 2 * nc + ne + ti * ((ne + 31) / 32);
-}
-int prep_tile(int ne, int nc) {
-  int ti = 64;
-  while (ti > 16 && ti * nc > 16384) ti >>= 1;
-  while (ti > 1 && prep_lds_words(ne, nc, ti) > 38 * 1024) ti >>= 1;
-  return ti;
 }
 
 // ------------------------------------------------------------------------------
@@ -3603,81 +2836,21 @@ hipError_t launch_hunk_tile(int mode, const HTileArgs& a, int B, hipStream_t st)
 int hunk_tile_cols() { return HTC; }
 int hunk_tile_rows() { return HTR; }
 
-}  // namespace hdg
-
-namespace {
-
-}  // namespace
-
-namespace hdg {
-
-thread_local char g_err[512] = "";
 thread_local KTrace* g_ktrace = nullptr;
 
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-hipError_t launch_prep_maps(const hdg_shape* s, const hdg_batch* bt, int stride, int o_ks,
-                            int o_kt, int o_ncst, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_prep_counts,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int ti = prep_tile(s->ne, s->nc);
-  const size_t lds = (size_t)prep_lds_words(s->ne, s->nc, ti) * 4;
-  uint32_t* prep = (uint32_t*)bt->prep;
-  hipLaunchKernelGGL(k_prep_ncst, dim3(s->batch), dim3(256), 0, st, prep, s->nc, stride, o_ncst,
-                     0);
-  hipLaunchKernelGGL(k_prep_counts, dim3((s->ne + ti - 1) / ti, s->batch, 2), dim3(512), lds, st,
-                     bt->abits, bt->hid, bt->nlen, prep, s->ne, s->nc, ti, stride, o_ks, o_kt,
-                     o_ncst);
-  hipLaunchKernelGGL(k_prep_ncst, dim3(s->batch), dim3(256), 0, st, prep, s->nc, stride, o_ncst,
-                     1);
-  return hipGetLastError();
-}
-
-// tf.global_variables() order per variant: E1 E3 | EE EC | H1 H2 TH
-Off param_offsets(int v) {
-  Off o;
-  memset(&o, 0xff, sizeof(o));   // -1 everywhere
-  if (v < 1 || v > 4) return o;
-  int p = 0;
-  if (v == 2 || v == 4) {
-    o.E1_W1 = p; p += 80;  o.E1_B1 = p; p += 20;  o.E1_W5 = p; p += 400; o.E1_B5 = p; p += 20;
-    o.E3_W1 = p; p += 420; o.E3_B1 = p; p += 20;  o.E3_W2 = p; p += 20;  o.E3_B2 = p; p += 1;
-  }
-  if (v == 3 || v == 4) {
-    o.EE_W11 = p; p += 20; o.EE_W12 = p; p += 40; o.EE_B1 = p; p += 20;
-    o.EE_W2 = p; p += 400; o.EE_B2 = p; p += 20;
-    o.EC_W1 = p; p += 440; o.EC_B1 = p; p += 20; o.EC_W2 = p; p += 40; o.EC_B2 = p; p += 2;
-  }
-  o.H1_W1 = p; p += 200; o.H1_B1 = p; p += 20; o.H1_W2 = p; p += 400; o.H1_B2 = p; p += 20;
-  o.H2_W1 = p; p += 440; o.H2_B1 = p; p += 20; o.H2_W2 = p; p += 40;  o.H2_B2 = p; p += 2;
-  o.TH1 = p; p += 2; o.TH2 = p; p += 2;
-  o.NP = p;
-  return o;
-}
-
 }  // namespace hdg
 
 namespace {
-
-using hdg::fail;
 
 bool fused_fits(const hdg_shape* s) {
   if ((s->variant != 2 && s->variant != 4) || s->ne > 256 || s->nc > 160) return false;
   const StepLayout L = step_layout(s->ne, s->nc, smax_c(s->nc));
   return (size_t)L.total * 4 <= 160 * 1024;
 }
+
+}  // namespace
+
+namespace hdg {
 
 // validates the shape; returns the resolved path (HDG_PATH_FUSED / _GENERAL) or -1
 int resolve(const hdg_shape* s) {
@@ -3700,21 +2873,22 @@ int resolve(const hdg_shape* s) {
   return fits ? HDG_PATH_FUSED : HDG_PATH_GENERAL;
 }
 
+int cu_count() {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+  return n;
+}
+
+}  // namespace hdg
+
+namespace {
+
 int check_batch(const hdg_batch* bt) {
   if (!bt || !bt->x || !bt->abits || !bt->ybits || !bt->hid || !bt->nlen || !bt->prep)
     return fail(HDG_EINVAL, "batch has a NULL device pointer");
   return 0;
 }
-
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) return fail((int)e_, "%s: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
-#define RESOLVE(s, var)                          \
-  const int var = resolve(s);                    \
-  if (var < 0) return HDG_EINVAL
 
 // Split mode (two blocks per commit, hunk rows split by parity, block-pair exchanges)
 // needs both blocks of a pair resident at once.  The host asks for it only when the
@@ -3724,13 +2898,6 @@ int check_batch(const hdg_batch* bt) {
 // loudly (xch_fault) rather than hanging.  A cooperative launch would check residency at
 // launch time but costs +17-20 us per replay (MI355X_MICROARCH price list), a quarter of
 // the step.  HDG_FUSED_SPLIT=0 forces one block per commit.
-int cu_count() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  return n;
-}
-
 template <int SMAXC, bool TRAIN, bool STAMPS, bool SPLIT>
 hipError_t set_step_attr() {
   static bool attr_set = false;   // the attribute is per function; 160 KiB covers every shape
@@ -3860,11 +3027,6 @@ hipError_t fused_ehr(const hdg_shape* s, float* ws, const Work& w, const float* 
   const size_t cs = (size_t)16 * smax_c(s->nc) * 16 * smax_c(s->nc);   // NC16^2 per commit
   return hdg::launch_ehr(ws + w.gam, ws + w.gam + (size_t)s->nc * HS, cs, s->batch, s->nc,
                          params, s->variant, out->ehr, st);
-}
-
-float pair_count(const hdg_shape* s) {
-  const int bg = s->batch_global > 0 ? s->batch_global : s->batch;
-  return (float)bg * (float)(s->nc * (s->nc - 1));
 }
 
 // ---- model_4 on the fused path ("hybrid"): the entity-edge stage runs on the general
@@ -4002,28 +3164,12 @@ int hdg_prep_counts_layout(const hdg_shape* s, int64_t* stride, int64_t* ks, int
   return 0;
 }
 
-int hdg_pack_classes(const uint8_t* cls, int32_t batch, int32_t n, uint32_t* bits,
-                     void* stream) {
-  if (!cls || !bits || batch < 1 || n < 1)
-    return fail(HDG_EINVAL, "hdg_pack_classes: NULL pointer or batch=%d n=%d", batch, n);
-  const int W = (n + 31) / 32;
-  const long long words = (long long)batch * n * W;
-  hipLaunchKernelGGL(k_pack_classes, dim3((unsigned)((words + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, cls, n, W, words, bits);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
 int hdg_prepare(const hdg_shape* s, const hdg_batch* bt, void* stream) {
   RESOLVE(s, path);
   if (int rc = check_batch(bt)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (path == HDG_PATH_GENERAL) return hdg::wide_prepare(s, bt, st);
-  hipLaunchKernelGGL(k_prep_sort, dim3(s->batch), dim3(256), 0, st, bt->x, bt->abits,
-                     (uint32_t*)bt->prep, s->ne, s->nc);
-  HIP_TRY(hipGetLastError());
-  const PrepLayout L = prep_layout(s->ne, s->nc);
-  HIP_TRY(hdg::launch_prep_maps(s, bt, L.words, L.ks, L.kt, L.ncst, st));
+  if (int rc = hdg::prep_fused(s, bt, st)) return rc;
   if (is_hybrid(s, path)) {        // + the general path's tables for the entity-edge stage
     const hdg_batch bw = wide_half(bt, s);
     return hdg::wide_prepare(s, &bw, st);
@@ -4168,257 +3314,6 @@ int hdg_forward(const hdg_shape* s, const hdg_batch* bt, const float* params, hd
   return 0;
 }
 
-// ---- data parallelism over xGMI ------------------------------------------------
-static_assert(sizeof(hipIpcMemHandle_t) == HDG_DP_HANDLE_BYTES, "IPC handle size");
-
-size_t hdg_dp_mailbox_bytes(void) { return dpk::BYTES; }
-
-// CRC-32C (Castagnoli, reflected 0x82F63B78), slicing by 8: the checksum of the TF V2
-// checkpoint bundle's records (hdgnn.tfckpt; LevelDB / TF masked CRCs)
-uint32_t hdg_crc32c(const void* data, size_t n, uint32_t crc) {
-  // slicing-by-8 tables, built once (a C++11 function-local static: thread-safe init)
-  struct Tab {
-    uint32_t t[8][256];
-    Tab() {
-      for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
-        t[0][i] = c;
-      }
-      for (uint32_t i = 0; i < 256; ++i)
-        for (int s = 1; s < 8; ++s) t[s][i] = (t[s - 1][i] >> 8) ^ t[0][t[s - 1][i] & 0xFFu];
-    }
-  };
-  static const Tab T;
-  const auto& tab = T.t;
-  const uint8_t* p = static_cast<const uint8_t*>(data);
-  uint32_t c = crc ^ 0xFFFFFFFFu;
-  for (; n >= 8; n -= 8, p += 8) {
-    uint32_t lo, hi;
-    memcpy(&lo, p, 4);
-    memcpy(&hi, p + 4, 4);
-    lo ^= c;
-    c = tab[7][lo & 0xFFu] ^ tab[6][(lo >> 8) & 0xFFu] ^ tab[5][(lo >> 16) & 0xFFu] ^
-        tab[4][lo >> 24] ^ tab[3][hi & 0xFFu] ^ tab[2][(hi >> 8) & 0xFFu] ^
-        tab[1][(hi >> 16) & 0xFFu] ^ tab[0][hi >> 24];
-  }
-  for (; n; --n, ++p) c = tab[0][(c ^ *p) & 0xFFu] ^ (c >> 8);
-  return c ^ 0xFFFFFFFFu;
-}
-
-static uint32_t mask_crc(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }
-
-static int write_file(const char* path, const void* p, size_t n) {
-  FILE* f = fopen(path, "wb");
-  if (!f) return fail(HDG_EINVAL, "cannot open %s for writing", path);
-  const size_t w = n ? fwrite(p, 1, n, f) : 0;
-  const int rc = fclose(f);
-  if (w != n || rc != 0) return fail(HDG_EINVAL, "short write to %s", path);
-  return 0;
-}
-
-int hdg_bundle_write(const char* data_path, const char* index_path, const float* state,
-                     int64_t n_state, const int32_t* gather, int64_t n_floats,
-                     uint8_t* index_img, int64_t index_len, const int64_t* entries,
-                     int32_t n_entries, const int64_t* blocks, int32_t n_blocks) {
-  if (!data_path || !index_path || !state || n_state < 0 || !gather || n_floats < 0 ||
-      !index_img || index_len < 48 || (n_entries && !entries) || (n_blocks && !blocks))
-    return fail(HDG_EINVAL, "hdg_bundle_write: bad arguments");
-  std::vector<float> blob((size_t)n_floats);
-  for (int64_t i = 0; i < n_floats; ++i) {
-    if (gather[i] < 0 || gather[i] >= n_state)
-      return fail(HDG_EINVAL, "hdg_bundle_write: gather[%lld] = %d outside the %lld-float state",
-                  (long long)i, (int)gather[i], (long long)n_state);
-    blob[i] = state[gather[i]];
-  }
-  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(blob.data());
-  const int64_t nbytes = n_floats * 4;
-  for (int32_t e = 0; e < n_entries; ++e) {        // entry proto field 6: masked CRC of bytes
-    const int64_t off = entries[3 * e], size = entries[3 * e + 1], pos = entries[3 * e + 2];
-    if (off < 0 || size < 0 || off + size > nbytes || pos < 0 || pos + 4 > index_len)
-      return fail(HDG_EINVAL, "hdg_bundle_write: entry %d out of range", (int)e);
-    const uint32_t c = mask_crc(hdg_crc32c(bytes + off, (size_t)size, 0));
-    memcpy(index_img + pos, &c, 4);
-  }
-  for (int32_t b = 0; b < n_blocks; ++b) {         // block trailer: type byte + masked CRC
-    const int64_t off = blocks[2 * b], len = blocks[2 * b + 1];
-    if (off < 0 || len < 0 || off + len + 5 > index_len)
-      return fail(HDG_EINVAL, "hdg_bundle_write: block %d out of range", (int)b);
-    const uint32_t c = mask_crc(hdg_crc32c(index_img + off, (size_t)len + 1, 0));
-    memcpy(index_img + off + len + 1, &c, 4);
-  }
-  // both files under temporary names first, then renamed data before index: a crash or a
-  // full disk mid-save never leaves a new .index beside a stale or partial .data
-  const std::string dtmp = std::string(data_path) + ".tmp", itmp = std::string(index_path) + ".tmp";
-  int rc = write_file(dtmp.c_str(), bytes, (size_t)nbytes);
-  if (!rc) rc = write_file(itmp.c_str(), index_img, (size_t)index_len);
-  if (!rc && rename(dtmp.c_str(), data_path) != 0)
-    rc = fail(HDG_EINVAL, "cannot rename %s to %s", dtmp.c_str(), data_path);
-  if (!rc && rename(itmp.c_str(), index_path) != 0)
-    rc = fail(HDG_EINVAL, "cannot rename %s to %s", itmp.c_str(), index_path);
-  if (rc) {
-    remove(dtmp.c_str());
-    remove(itmp.c_str());
-  }
-  return rc;
-}
-
-// ---- background checkpoint writer -------------------------------------------------
-// saver.save off the training thread: one native thread writes the queued bundles (and the
-// small text files that go with them) in submission order, so the training loop's thread
-// only copies the state into the job.  The first failure is kept for flush().
-struct CkptJob {
-  std::vector<float> state;                  // empty: no bundle in this job
-  std::string data_path, index_path, removes, text_path, text;
-  bool text_append = false;
-};
-struct hdg_ckpt_writer_s {
-  std::vector<int32_t> gather;
-  std::vector<uint8_t> image;
-  std::vector<int64_t> entries, blocks;
-  int64_t n_state = 0;
-  std::mutex mu;
-  std::condition_variable cv, idle;
-  std::deque<CkptJob> q;
-  bool busy = false, stop = false;
-  int err_code = 0;
-  char err[512] = "";
-  std::thread th;
-};
-
-static int ckpt_run(hdg_ckpt_writer_s* w, CkptJob& j) {
-  if (!j.state.empty()) {
-    std::vector<uint8_t> img = w->image;     // the CRCs are patched into a private copy
-    if (int rc = hdg_bundle_write(j.data_path.c_str(), j.index_path.c_str(), j.state.data(),
-                                  (int64_t)j.state.size(), w->gather.data(),
-                                  (int64_t)w->gather.size(), img.data(), (int64_t)img.size(),
-                                  w->entries.data(), (int32_t)(w->entries.size() / 3),
-                                  w->blocks.data(), (int32_t)(w->blocks.size() / 2)))
-      return rc;
-  }
-  size_t a = 0;                              // '\n'-separated paths: missing ones are fine
-  while (a < j.removes.size()) {
-    size_t e = j.removes.find('\n', a);
-    if (e == std::string::npos) e = j.removes.size();
-    if (e > a) remove(j.removes.substr(a, e - a).c_str());
-    a = e + 1;
-  }
-  if (!j.text_path.empty()) {
-    FILE* f = fopen(j.text_path.c_str(), j.text_append ? "ab" : "wb");
-    if (!f) return fail(HDG_EINVAL, "cannot open %s for writing", j.text_path.c_str());
-    const size_t n = j.text.size(), wr = n ? fwrite(j.text.data(), 1, n, f) : 0;
-    if (fclose(f) != 0 || wr != n) return fail(HDG_EINVAL, "short write to %s", j.text_path.c_str());
-  }
-  return 0;
-}
-
-static void ckpt_loop(hdg_ckpt_writer_s* w) {
-  std::unique_lock<std::mutex> lk(w->mu);
-  for (;;) {
-    w->cv.wait(lk, [&] { return w->stop || !w->q.empty(); });
-    if (w->q.empty()) return;                // stop with nothing queued
-    CkptJob j = std::move(w->q.front());
-    w->q.pop_front();
-    w->busy = true;
-    lk.unlock();
-    const int rc = ckpt_run(w, j);
-    lk.lock();
-    if (rc && !w->err_code) {
-      w->err_code = rc;
-      snprintf(w->err, sizeof(w->err), "%s", hdg::g_err);
-    }
-    w->busy = false;
-    if (w->q.empty()) w->idle.notify_all();
-  }
-}
-
-int hdg_ckpt_writer_create(const int32_t* gather, int64_t n_floats, int64_t n_state,
-                           const uint8_t* index_img, int64_t index_len, const int64_t* entries,
-                           int32_t n_entries, const int64_t* blocks, int32_t n_blocks,
-                           void** writer) {
-  if (!writer || !gather || n_floats < 0 || n_state < 0 || !index_img || index_len < 48 ||
-      (n_entries && !entries) || (n_blocks && !blocks))
-    return fail(HDG_EINVAL, "hdg_ckpt_writer_create: bad arguments");
-  for (int64_t i = 0; i < n_floats; ++i)
-    if (gather[i] < 0 || gather[i] >= n_state)
-      return fail(HDG_EINVAL, "hdg_ckpt_writer_create: gather[%lld] outside the state",
-                  (long long)i);
-  auto* w = new hdg_ckpt_writer_s;
-  w->gather.assign(gather, gather + n_floats);
-  w->image.assign(index_img, index_img + index_len);
-  w->entries.assign(entries, entries + 3 * (size_t)n_entries);
-  w->blocks.assign(blocks, blocks + 2 * (size_t)n_blocks);
-  w->n_state = n_state;
-  w->th = std::thread(ckpt_loop, w);
-  *writer = w;
-  return 0;
-}
-
-int hdg_ckpt_writer_submit(void* writer, const float* state, const char* data_path,
-                           const char* index_path, const char* removes, const char* text_path,
-                           const char* text, int32_t text_append) {
-  auto* w = static_cast<hdg_ckpt_writer_s*>(writer);
-  if (!w || (state && (!data_path || !index_path)) || (text_path && !text))
-    return fail(HDG_EINVAL, "hdg_ckpt_writer_submit: bad arguments");
-  CkptJob j;
-  if (state) {
-    j.state.assign(state, state + w->n_state);
-    j.data_path = data_path;
-    j.index_path = index_path;
-  }
-  if (removes) j.removes = removes;
-  if (text_path) {
-    j.text_path = text_path;
-    j.text = text;
-    j.text_append = text_append != 0;
-  }
-  {
-    std::lock_guard<std::mutex> lk(w->mu);
-    w->q.push_back(std::move(j));
-  }
-  w->cv.notify_one();
-  return 0;
-}
-
-int hdg_ckpt_writer_flush(void* writer) {
-  auto* w = static_cast<hdg_ckpt_writer_s*>(writer);
-  if (!w) return fail(HDG_EINVAL, "hdg_ckpt_writer_flush: NULL writer");
-  std::unique_lock<std::mutex> lk(w->mu);
-  w->idle.wait(lk, [&] { return w->q.empty() && !w->busy; });
-  const int rc = w->err_code;
-  if (rc) {
-    snprintf(hdg::g_err, sizeof(hdg::g_err), "%s", w->err);
-    w->err_code = 0;                         // reported once, as a future's exception is
-  }
-  return rc;
-}
-
-int hdg_ckpt_writer_poll(void* writer) {
-  auto* w = static_cast<hdg_ckpt_writer_s*>(writer);
-  if (!w) return fail(HDG_EINVAL, "hdg_ckpt_writer_poll: NULL writer");
-  std::lock_guard<std::mutex> lk(w->mu);
-  const int rc = w->err_code;
-  if (rc) {
-    snprintf(hdg::g_err, sizeof(hdg::g_err), "%s", w->err);
-    w->err_code = 0;
-  }
-  return rc;
-}
-
-int hdg_ckpt_writer_destroy(void* writer) {
-  auto* w = static_cast<hdg_ckpt_writer_s*>(writer);
-  if (!w) return 0;
-  const int rc = hdg_ckpt_writer_flush(w);
-  {
-    std::lock_guard<std::mutex> lk(w->mu);
-    w->stop = true;
-  }
-  w->cv.notify_all();
-  w->th.join();
-  delete w;
-  return rc;
-}
-
 // stream-ordered copy and completion events for the training loop's host reads (the same
 // HIP calls torch's copy_ / Event make, without the dispatcher on every epoch)
 int hdg_memcpy_async(void* dst, const void* src, size_t bytes, void* stream) {
@@ -4443,127 +3338,7 @@ int hdg_event_destroy(void* ev) {
   return 0;
 }
 
-int hdg_dp_mailbox_alloc(void** mailbox, void* handle) {
-  if (!mailbox || !handle) return fail(HDG_EINVAL, "NULL mailbox/handle pointer");
-  *mailbox = nullptr;
-  // uncached: the peers' write-through words and this rank's polling loads meet in memory
-  HIP_TRY(hipExtMallocWithFlags(mailbox, dpk::BYTES, hipDeviceMallocUncached));
-  hipIpcMemHandle_t h;
-  hipError_t e = hipMemset(*mailbox, 0, dpk::BYTES);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipIpcGetMemHandle(&h, *mailbox);
-  if (e != hipSuccess) {
-    (void)hipFree(*mailbox);
-    *mailbox = nullptr;
-    return fail((int)e, "mailbox setup: %s", hipGetErrorString(e));
-  }
-  memcpy(handle, &h, sizeof(h));
-  return 0;
-}
-
-int hdg_dp_mailbox_open(const void* handle, void** mailbox) {
-  if (!mailbox || !handle) return fail(HDG_EINVAL, "NULL mailbox/handle pointer");
-  hipIpcMemHandle_t h;
-  memcpy(&h, handle, sizeof(h));
-  *mailbox = nullptr;
-  HIP_TRY(hipIpcOpenMemHandle(mailbox, h, hipIpcMemLazyEnablePeerAccess));
-  return 0;
-}
-
-int hdg_dp_mailbox_close(void* mailbox) {
-  HIP_TRY(hipIpcCloseMemHandle(mailbox));
-  return 0;
-}
-
-int hdg_dp_mailbox_free(void* mailbox) {
-  HIP_TRY(hipFree(mailbox));
-  return 0;
-}
-
-}  // extern "C"
-
-namespace {
-int dp_args(const hdg_dp* dp, DpArgs& a) {
-  if (!dp) return fail(HDG_EINVAL, "NULL hdg_dp");
-  if (dp->world < 1 || dp->world > HDG_DP_MAX_WORLD || dp->rank < 0 || dp->rank >= dp->world)
-    return fail(HDG_EINVAL, "hdg_dp: rank %d / world %d out of range (world <= %d)", dp->rank,
-                dp->world, HDG_DP_MAX_WORLD);
-  if (dp->flags & ~HDG_DP_SHARED) return fail(HDG_EINVAL, "hdg_dp: unknown flags 0x%x", dp->flags);
-  memset(&a, 0, sizeof(a));
-  for (int r = 0; r < dp->world; ++r) {
-    if (!dp->mailbox[r]) return fail(HDG_EINVAL, "hdg_dp: mailbox of rank %d is NULL", r);
-    a.box[r] = (uint32_t*)dp->mailbox[r];
-  }
-  a.rank = dp->rank;
-  a.world = dp->world;
-  a.wait = dp->wait_ticks ? dp->wait_ticks : dpk::WAIT_DEFAULT;
-  return 0;
-}
-bool dp_shared(const hdg_dp* dp) { return (dp->flags & HDG_DP_SHARED) != 0; }
-// blocks per rank of the shared-device tail: as many as keep the W - 1 waiting ranks'
-// spinning blocks on at most half of the CUs (at least HDG_DP_SHARED_BLOCKS: 15 x 8 = 120
-// <= 128 at HDG_DP_MAX_WORLD), at most one per slot group
-unsigned dp_shared_grid(int n, int world) {
-  const int groups = (n + RED_P - 1) / RED_P;
-  const int cus = cu_count() > 0 ? cu_count() : 256;
-  int g = cus / (2 * (world > 1 ? world - 1 : 1));
-  if (g < HDG_DP_SHARED_BLOCKS) g = HDG_DP_SHARED_BLOCKS;
-  return (unsigned)(groups < g ? groups : g);
-}
-float* dp_aux(const hdg_dp* dp) {
-  return (float*)((char*)dp->mailbox[dp->rank] + dpk::OFF_AUX);
-}
-}  // namespace
-
-extern "C" {
-
-int hdg_dp_allreduce(const hdg_dp* dp, const float* in, float* out, int32_t n, uint32_t* status,
-                     void* stream) {
-  DpArgs a;
-  if (int rc = dp_args(dp, a)) return rc;
-  if (!in || !out || n < 1 || n > HDG_DP_MAX_LEN)
-    return fail(HDG_EINVAL, "hdg_dp_allreduce: NULL buffer or n=%d outside [1, %d]", n,
-                HDG_DP_MAX_LEN);
-  if (dp_shared(dp))
-    hipLaunchKernelGGL(k_dp_tail_shared<dpk::SUM>, dim3(dp_shared_grid(n, a.world)), dim3(DP_NT_LIGHT), 0,
-                       (hipStream_t)stream, in, 0, n, out, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, 0.f, 0.f, nullptr, status, a);
-  else
-    hipLaunchKernelGGL(k_dp_tail<dpk::SUM>, dim3((n + RED_P - 1) / RED_P), dim3(DP_NT_LIGHT), 0,
-                       (hipStream_t)stream, in, 1, 0, n, out, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, 0.f, 0.f, nullptr, status, 0, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int hdg_adam_dp(const hdg_shape* s, hdg_state* state, const float* grad_local, float* grad_out,
-                float lr, float* stats, uint32_t* status, const hdg_dp* dp, void* stream) {
-  RESOLVE(s, path);
-  (void)path;
-  DpArgs a;
-  if (int rc = dp_args(dp, a)) return rc;
-  if (!state || !state->params || !state->adam_m || !state->adam_v || !state->beta_pow ||
-      !grad_local || !grad_out)
-    return fail(HDG_EINVAL, "NULL state/grad pointer");
-  const int np = hdg::param_offsets(s->variant).NP, glen = np + HDG_TRAILER;
-  hipStream_t st = (hipStream_t)stream;
-  float* aux = dp_aux(dp);
-  hipLaunchKernelGGL(k_dp_aux, dim3(1), dim3(1024), 0, st, state->params, np, state->beta_pow,
-                     aux);
-  if (dp_shared(dp))
-    hipLaunchKernelGGL(k_dp_tail_shared<dpk::GRAD>, dim3(dp_shared_grid(glen, a.world)), dim3(DP_NT_LIGHT),
-                       0, st, grad_local, np, glen, grad_out, state->params, state->adam_m,
-                       state->adam_v, state->beta_pow, aux, lr, 1.f / pair_count(s), stats,
-                       status, a);
-  else
-    hipLaunchKernelGGL(k_dp_tail<dpk::GRAD>, dim3((glen + RED_P - 1) / RED_P), dim3(DP_NT_LIGHT),
-                       0, st, grad_local, 1, np, glen, grad_out, state->params, state->adam_m,
-                       state->adam_v, state->beta_pow, aux, lr, 1.f / pair_count(s), stats,
-                       status, 0, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
+// data-parallel training step: this rank's step, then the tail over xGMI (dp.hip)
 int hdg_train_step_dp(const hdg_shape* s, const hdg_batch* bt, hdg_state* state, float lr,
                       hdg_outputs* out, float* grad, void* workspace, const hdg_dp* dp,
                       void* stream) {
@@ -4572,8 +3347,7 @@ int hdg_train_step_dp(const hdg_shape* s, const hdg_batch* bt, hdg_state* state,
   RESOLVE(s, path);
   if (int rc = check_batch(bt)) return rc;
   if (!grad || !workspace) return fail(HDG_EINVAL, "NULL grad/workspace");
-  DpArgs a;
-  if (int rc = dp_args(dp, a)) return rc;
+  if (int rc = hdg::dp_check(dp)) return rc;
   hipStream_t st = (hipStream_t)stream;
   uint32_t* status = out ? out->status : nullptr;
   float* stats = out ? out->stats : nullptr;
@@ -4582,7 +3356,7 @@ int hdg_train_step_dp(const hdg_shape* s, const hdg_batch* bt, hdg_state* state,
     // reads it while other blocks already write the world sums into grad).  Ranks that
     // share a device take this route on the fused path too: the partial rows are reduced
     // by the non-spinning k_grad_reduce, and only the light tail waits for the peers
-    float* local = (float*)((char*)dp->mailbox[dp->rank] + dpk::OFF_GLOC);
+    float* local = hdg::dp_local_grad(dp);
     const int rc = path == HDG_PATH_GENERAL
         ? hdg::wide_run(s, bt, state->params, local, out, nullptr, workspace, true, st)
         : is_hybrid(s, path)
@@ -4598,12 +3372,9 @@ int hdg_train_step_dp(const hdg_shape* s, const hdg_batch* bt, hdg_state* state,
   const bool split = use_split(s);
   HIP_TRY(dispatch_step<true>(s, bt, state->params, ws, w, step_out(out), 10.f / pairs, nullptr,
                               st, split, state->beta_pow));
-  hipLaunchKernelGGL(k_dp_tail<dpk::PART>, dim3((GRAD_LEN + RED_P - 1) / RED_P), dim3(1024), 0,
-                     st, ws + w.part, part_rows(s, split), m2::NP, GRAD_LEN, grad, state->params,
-                     state->adam_m, state->adam_v, state->beta_pow, ws + w.aux, lr, 1.f / pairs,
-                     stats, status, split ? part_rows(s, split) : 0, a);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return hdg::launch_dp_tail_part(dp, ws + w.part, part_rows(s, split),
+                                  split ? part_rows(s, split) : 0, grad, state, ws + w.aux, lr,
+                                  1.f / pairs, stats, status, st);
 }
 
 }  // extern "C"

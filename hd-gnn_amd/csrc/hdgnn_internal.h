@@ -1,10 +1,18 @@
-// hdgnn_internal.h -- declarations shared by the two engine paths of libhdgnn.so
+// hdgnn_internal.h -- declarations shared by the translation units of libhdgnn.so
 // (not part of the public C ABI; see include/hdgnn.h).
 //
 //   fused path   hdgnn.hip  one 1024-thread block per commit, LDS-resident commit state;
-//                           model_2 with ne <= 256, nc <= 160 (the benchmark shape)
+//                           model_2 with ne <= 256, nc <= 160 (the benchmark shape); path
+//                           resolution, sizing and the step entry points
 //   general path wide.hip   any ne / nc, model variants 1-4, one phase per launch with
 //                           many 256-thread blocks per commit, state in HBM
+//   batch prep   prep.hip   the parameter-independent tables of an uploaded batch
+//   dp tail      dp.hip     the data-parallel tail over xGMI and its mailbox API
+//   evaluation   eval.hip   on-device confusion counts and ROC-AUC
+//   host only    ckpt.cpp   CRC-32C and the checkpoint bundle writer (err.h alone)
+//
+//   xlane.h       cross-lane / packed-math device primitives of every path
+//   fused_tail.h  the fused path's partial-row reduction, shared by hdgnn.hip and dp.hip
 #ifndef HDGNN_INTERNAL_H
 #define HDGNN_INTERNAL_H
 
@@ -13,6 +21,20 @@
 #include <stdint.h>
 
 #include "hdgnn.h"
+#include "err.h"
+#include "xlane.h"
+
+// entry points: return a HIP error (message set) / return HDG_EINVAL for a rejected shape;
+// both expect hdg::fail and hdg::resolve in scope
+#define HIP_TRY(expr)                                                                     \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) return fail((int)e_, "%s: %s", #expr, hipGetErrorString(e_));   \
+  } while (0)
+
+#define RESOLVE(s, var)                          \
+  const int var = resolve(s);                    \
+  if (var < 0) return HDG_EINVAL
 
 namespace hdg {
 
@@ -76,7 +98,28 @@ struct Off {
   int TH1, TH2, NP;                          // map_conv thetas, parameter count
 };
 
-Off param_offsets(int variant);   // NP = -1 for an unknown variant
+// tf.global_variables() order per variant: E1 E3 | EE EC | H1 H2 TH;
+// NP = -1 for an unknown variant
+constexpr Off param_offsets(int v) {
+  Off o = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
+           -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  if (v < 1 || v > 4) return o;
+  int p = 0;
+  if (v == 2 || v == 4) {
+    o.E1_W1 = p; p += 80;  o.E1_B1 = p; p += 20;  o.E1_W5 = p; p += 400; o.E1_B5 = p; p += 20;
+    o.E3_W1 = p; p += 420; o.E3_B1 = p; p += 20;  o.E3_W2 = p; p += 20;  o.E3_B2 = p; p += 1;
+  }
+  if (v == 3 || v == 4) {
+    o.EE_W11 = p; p += 20; o.EE_W12 = p; p += 40; o.EE_B1 = p; p += 20;
+    o.EE_W2 = p; p += 400; o.EE_B2 = p; p += 20;
+    o.EC_W1 = p; p += 440; o.EC_B1 = p; p += 20; o.EC_W2 = p; p += 40; o.EC_B2 = p; p += 2;
+  }
+  o.H1_W1 = p; p += 200; o.H1_B1 = p; p += 20; o.H1_W2 = p; p += 400; o.H1_B2 = p; p += 20;
+  o.H2_W1 = p; p += 440; o.H2_B1 = p; p += 20; o.H2_W2 = p; p += 40;  o.H2_B2 = p; p += 2;
+  o.TH1 = p; p += 2; o.TH2 = p; p += 2;
+  o.NP = p;
+  return o;
+}
 
 // general path (wide.hip)
 // A single-process training step's TF-Adam tail run inside the general path's final
@@ -147,10 +190,30 @@ hipError_t launch_hunk_tile(int mode, const HTileArgs& a, int B, hipStream_t st)
 int hunk_tile_cols();             // HTC: columns per block
 int hunk_tile_rows();             // HTR: rows per block
 
-// fused path pieces the general path reuses (hdgnn.hip)
+// shape checks and device facts every translation unit's entry points use (hdgnn.hip)
+int resolve(const hdg_shape* s);   // the resolved path (HDG_PATH_FUSED / _GENERAL) or -1
+int cu_count();
+inline float pair_count(const hdg_shape* s) {
+  const int bg = s->batch_global > 0 ? s->batch_global : s->batch;
+  return (float)bg * (float)(s->nc * (s->nc - 1));
+}
+
+// batch prep (prep.hip): the cross-graph count tables of both paths' layouts, and the
+// whole fused-layout prep (k_prep_sort + the count tables at prep_layout's offsets)
 hipError_t launch_prep_maps(const hdg_shape* s, const hdg_batch* bt, int stride, int o_ks,
                             int o_kt, int o_ncst, hipStream_t st);
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int prep_fused(const hdg_shape* s, const hdg_batch* bt, hipStream_t st);
+
+// data-parallel tail (dp.hip) for hdg_train_step_dp.  dp_check validates an hdg_dp (0, or
+// HDG_EINVAL with the message set); dp_local_grad is the mailbox's scratch for the rank's
+// own reduced gradient; launch_dp_tail_part runs the fused path's reduction + exchange +
+// Adam (k_dp_tail<PART>) on the step kernel's rows partial rows at part.
+int dp_check(const hdg_dp* dp);
+bool dp_shared(const hdg_dp* dp);
+float* dp_local_grad(const hdg_dp* dp);
+int launch_dp_tail_part(const hdg_dp* dp, const float* part, int rows, int fault_rows,
+                        float* grad, hdg_state* state, const float* aux, float lr,
+                        float inv_pairs, float* stats, uint32_t* status, hipStream_t st);
 
 // Per-kernel timing hook (hdg_fwd_bwd_kernel_events): while a traced call runs, every
 // launch site of the step records one event after its launch, so events[k] .. events[k+1]
@@ -168,50 +231,6 @@ inline hipError_t kmark(const char* name, hipStream_t st) {
   if (e != hipSuccess || !t || t->n + 1 >= t->cap) return e;
   t->names[t->n++] = name;
   return hipEventRecord((hipEvent_t)t->ev[t->n], st);
-}
-
-// ------------------------------------------------------------------------------
-// MFMA 16x16 fp32 tile (v_mfma_f32_16x16x4_f32) used by both paths
-// ------------------------------------------------------------------------------
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// The same tile with strided operands: lane l supplies row r = l & 15 of A as
-// pa[k * sa] and column r of B as pb[k * sb], k < K.  A row / column outside the matrix
-// passes a pointer to a 0.f word with stride 0 (a row of ones: a 1.f word, stride 0), so
-// the K loop carries no bounds logic: one LDS read and one address add per operand.
-__device__ __forceinline__ f4v mfma_tile16_p(const float* pa, const int sa, const float* pb,
-                                             const int sb, const int K, const int lane) {
-  const int q = lane >> 4;
-  const float* a = pa + q * sa;
-  const float* b = pb + q * sb;
-  const int sa4 = 4 * sa, sb4 = 4 * sb;
-  f4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
-  int k = 0;
-  for (; k + 16 <= K; k += 16) {
-    float av[4], bv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      av[u] = a[u * sa4];
-      bv[u] = b[u * sb4];
-    }
-    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], c1, 0, 0, 0);
-    a += 4 * sa4;
-    b += 4 * sb4;
-  }
-  for (; k + 4 <= K; k += 4) {
-    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c0, 0, 0, 0);
-    a += sa4;
-    b += sb4;
-  }
-  if (k < K) {                       // K % 4 tail: entries k + q >= K are selected to zero
-    const bool ok = k + q < K;       // (callers' arrays are padded, the read stays in LDS)
-    const float av = ok ? a[0] : 0.f, bv = ok ? b[0] : 0.f;
-    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, c0, 0, 0, 0);
-  }
-  return c0 + c1;
 }
 
 }  // namespace hdg

@@ -55,7 +55,6 @@ constexpr int NT = 256;     // threads per block
 constexpr int NW = NT / 64;
 constexpr double FIX = 4294967296.0;   // 2^32 fixed-point scale of the hunk bins
 
-__device__ __forceinline__ float relu(float v) { return fmaxf(v, 0.f); }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Wave time stamps of one kernel (timing builds only: -DHDG_WSTAMP=<kernel id>, read by
@@ -85,22 +84,6 @@ __device__ unsigned long long* g_wst;
 #define HDG_ABL_XJ 0  // (wrong sums; for timing the LDS gathers of the walks)
 #endif
 
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v),
-                                                               CTRL, 0xF, 0xF, false));
-}
-// v_permlane32_swap / v_permlane16_swap (VALU, no LDS): swap32 trades x's lanes 32-63 for
-// y's lanes 0-31, swap16 x's rows 1, 3 for y's rows 0, 2 (inline asm: the ROCm 7.2
-// builtins mis-assign the two results; two wait states after a VALU write of the operands)
-__device__ __forceinline__ void swap32(float& x, float& y) {
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-__device__ __forceinline__ void swap16(float& x, float& y) {
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-
 // wave sum by a VALU butterfly (permlane swaps across the 32- / 16-lane halves, DPP inside
 // a row): every lane ends with the same total (each level adds the same two partial
 // sums in every lane, and fp32 addition commutes)
@@ -116,14 +99,6 @@ __device__ __forceinline__ float wsum(float v) {
   v += dppf<0x141>(v);   // row_half_mirror  7 - lane (per 8)
   v += dppf<0x4E>(v);    // quad_perm        lane ^ 2
   v += dppf<0xB1>(v);    // quad_perm        lane ^ 1
-  return v;
-}
-// sum over a 16-lane DPP row; every lane of the row receives the total
-__device__ __forceinline__ float row_total16(float v) {
-  v += dppf<0x128>(v);
-  v += dppf<0x141>(v);
-  v += dppf<0x4E>(v);
-  v += dppf<0xB1>(v);
   return v;
 }
 
@@ -513,35 +488,10 @@ constexpr int NTP = 512;
 constexpr int NWP = NTP / 64;
 constexpr int CHM = 128;
 constexpr int H2 = H / 2;
-typedef float f2 __attribute__((ext_vector_type(2)));
 
+// packed-pair helpers beside xlane.h's f2, step2, stepf2
 __device__ __forceinline__ f2 relu2(f2 v) { return __builtin_elementwise_max(v, (f2){0.f, 0.f}); }
-// [z > 0] on both halves in one op: clamp(z * 2^126, 0, 1) (exact for normal z; -0, NaN -> 0)
-__device__ __forceinline__ f2 step2(f2 z) {
-  f2 r;
-  asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(z), "v"((f2){0x1p126f, 0x1p126f}));
-  return r;
-}
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-// ln x for x in [1, 2] (the two-class CE's log(1 + e^-|d|) and log(e0 + e1)): v_log_f32
-// (log2, ~1 ulp, no denormal range to guard) times ln 2 -- 2 VALU ops where logf expands to
-// a denormal-scaled, split-constant sequence of ~11
-__device__ __forceinline__ float ln_1to2(float x) { return __builtin_amdgcn_logf(x) * 0.693147182f; }
-// [x + c > 0] for a packed pair in ONE op where only the step of the sum is used (not the
-// sum): clamp(fma(x, 2^64, c 2^64)).  The fma rounds the exact (x + c) 2^64 once, so the
-// result is 0 for x + c <= 0 (-0, NaN: 0) and 1 for every x + c >= 2^-64; it differs from
-// step2(fl(x + c)) only for 0 < x + c < 2^-64.  cs = c 2^64 (exact and finite for |c| <
-// 2^63; -inf masks the pair).
-#ifndef HDG_STEPF
-#define HDG_STEPF 1
-#endif
-constexpr float STEP_S = 0x1p64f;
-__device__ __forceinline__ f2 stepf2(f2 x, f2 cs) {
-  f2 r;
-  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp"
-      : "=v"(r) : "v"(x), "s"((f2){STEP_S, STEP_S}), "v"(cs));
-  return r;
-}
 __device__ __forceinline__ f2 ld2(const float* p) { return (f2){p[0], p[1]}; }
 
 // rows [c0, c1) of a [N][H] array -> LDS (float4 copies; rows are 80 B, 16-B aligned)
@@ -692,8 +642,6 @@ __host__ __device__ inline size_t sort_lds_bytes(int Ne) {
   const size_t NE4 = (Ne + 3) & ~3;
   return (NE4 + 4) * 8 + (NE4 + 4) * 4 + (2 * NE4 + 4) * 4;   // pxd, cum, xu, x (+ sentinel)
 }
-
-__device__ __forceinline__ int top_pow2(int n) { return 1 << (31 - __builtin_clz((unsigned)n)); }
 
 // boundary q of the set {distinct values v : pred(v)} when pred is monotone: with
 // inc = pred increasing in v the set is [q, nd) (suffix), otherwise [0, q) (prefix);
@@ -1317,7 +1265,7 @@ __global__ __launch_bounds__(64 * NWF) void kw_ee_fwd(const uint32_t* __restrict
     // DPP row q of the wave ends with half q >> 1's sum of p_(q & 1)
     float x = p0, y = p1;
     swap16(x, y);
-    const float v = row_total16(x + y);
+    const float v = row16_sum<ROW_ROR8>(x + y);
     if ((lane & 15) == 0 && jp < jhi) tsum[2 * jp + ((lane >> 4) & 1)] = v;
   }
   prio0_e();

@@ -12,12 +12,20 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
+# every translation unit of libhdgnn.so, in csrc/ (the one list: the hazard scan and the
+# host-sanitizer build of the tests take theirs from here)
+SOURCES = ("hdgnn.hip", "wide.hip", "eval.hip", "dp.hip", "prep.hip", "ckpt.cpp")
+
+
+def device_sources():
+    return tuple(f for f in SOURCES if f.endswith(".hip"))
 
 
 def build(verbose=False, out=None, force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("hdgnn.hip", "wide.hip", "eval.hip")]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES]
     out = out or os.path.join(CSRC, "libhdgnn.so")
-    deps = srcs + [os.path.join(CSRC, "hdgnn_internal.h"), os.path.join(ROOT, "include", "hdgnn.h")]
+    deps = srcs + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
+    deps.append(os.path.join(ROOT, "include", "hdgnn.h"))
     extra = os.environ.get("HDG_HIPCC_FLAGS", "").split()   # experiments (A/B builds)
     # the effective flags are stamped next to the library: a build with other flags (an A/B
     # experiment, or the default after one) is never mistaken for an up-to-date one

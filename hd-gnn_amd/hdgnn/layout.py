@@ -2,7 +2,8 @@
 
 model_2.py:161-179 phi_E_O1, 190-205 phi_U_O1, 245-277 mlp_hunk_B2, 304-324 phi_U_R1,
 326-333 map_conv; model_4.py:206-243 phi_E_R1, 286-304 phi_U_R1 (entity-edge blocks).
-Offsets match hdg::param_offsets in csrc/hdgnn.hip (and m2:: for model_2).
+Offsets match hdg::param_offsets in csrc/hdgnn_internal.h (and m2:: in csrc/fused_tail.h
+for model_2).
 """
 import numpy as np
 

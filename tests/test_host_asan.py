@@ -10,6 +10,7 @@ failed check fails the test.  Skipped when the ROCm toolchain is absent.
 import os
 import shutil
 import subprocess
+import sys
 
 import pytest
 
@@ -22,14 +23,15 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang"
                     reason="ROCm toolchain absent")
 @pytest.mark.timeout(900)
 def test_abi_host_asan_ubsan(tmp_path):
-    csrc = os.path.join(ROOT, "hd-gnn_amd", "csrc")
+    sys.path.insert(0, os.path.join(ROOT, "hd-gnn_amd"))
+    from hdgnn import build as hdg_build
     inc = os.path.join(ROOT, "include")
     lib = tmp_path / "libhdgnn_asan.so"
     san = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
            "-Xarch_host", "-fno-omit-frame-pointer", "-Xarch_host", "-g"]
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-shared",
-                    "-I" + inc] + san + ["-o", str(lib), os.path.join(csrc, "hdgnn.hip"),
-                                         os.path.join(csrc, "wide.hip")],
+                    "-I" + inc] + san + ["-o", str(lib)] +
+                   [os.path.join(hdg_build.CSRC, f) for f in hdg_build.SOURCES],
                    check=True, timeout=800)
     exe = tmp_path / "asan_abi"
     subprocess.run([CLANG, "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",

@@ -1,10 +1,10 @@
 """The device code's hand-written cross-lane instructions keep their wait states.
 
-row16_sums / swap16 / swap32 (hdgnn.hip, wide.hip) are inline asm, which the compiler's
-hazard recognizer does not see into; a DPP or permlane-swap read issued < 2 wait states
-after the VALU write of its operand returns stale lanes -- wrong sums whose presence
-depends on the schedule.  Compiles both sources to gfx950 assembly (CPU only) and scans
-every cross-lane read with tools/dpp_hazards.py.
+row16_sums (hdgnn.hip) and swap16 / swap32 (xlane.h, every path) are inline asm, which the
+compiler's hazard recognizer does not see into; a DPP or permlane-swap read issued < 2 wait
+states after the VALU write of its operand returns stale lanes -- wrong sums whose presence
+depends on the schedule.  Compiles every device source of the library (hdgnn.build.SOURCES)
+to gfx950 assembly (CPU only) and scans every cross-lane read with tools/dpp_hazards.py.
 """
 import os
 import shutil
@@ -22,9 +22,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 @pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not available")
 def test_no_cross_lane_read_hazards(tmp_path):
     import dpp_hazards
-    csrc = os.path.join(ROOT, "hd-gnn_amd", "csrc")
+    from hdgnn import build as hdg_build
+    csrc = hdg_build.CSRC
     procs, outs = [], []
-    for f in ("hdgnn.hip", "wide.hip"):
+    for f in hdg_build.device_sources():
         out = str(tmp_path / (f + ".s"))
         outs.append(out)
         procs.append(subprocess.Popen(
@@ -36,8 +37,9 @@ def test_no_cross_lane_read_hazards(tmp_path):
         assert p.returncode == 0, err.decode(errors="replace")[-2000:]
     bad = [(o, b) for o in outs for b in dpp_hazards.scan(o)]
     assert not bad, bad[:5]
-    # the scan sees the hand-written reductions (guards against a vacuous pass)
-    text = open(outs[0]).read()
+    # the scan sees the hand-written reductions (guards against a vacuous pass): the
+    # assembly of the translation unit that holds k_commit_step
+    (text,) = [t for t in (open(o).read() for o in outs) if "k_commit_step" in t]
     assert text.count("v_add_f32_dpp") > 100 and "v_permlane16_swap_b32" in text
 
 

@@ -2,8 +2,8 @@
 operand (DPP src0 / v_permlane*_swap operands need 2 wait states after it).
 
 The compiler inserts these wait states for the cross-lane instructions it emits itself but
-cannot see inside inline asm; hdgnn.hip's row16_sums / swap helpers carry their own
-s_nop.  A violation reads the operand's previous value on some lanes: silently wrong sums
+cannot see inside inline asm; hdgnn.hip's row16_sums and xlane.h's swap helpers carry their
+own s_nop.  A violation reads the operand's previous value on some lanes: silently wrong sums
 that depend on the schedule (how the round-2 pair_tile32 "wrong pass B" results arose).
 
     python tools/dpp_hazards.py file.s [...]          # prints violations, exit 1 if any

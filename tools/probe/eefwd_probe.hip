@@ -2,7 +2,8 @@
 // Nc=74, n uniform in [Ne/2, 3Ne/2] clipped to Ne as hdgnn/synth.py draws it), per-wave
 // s_memrealtime stamps at the phase boundaries (100 MHz clock).
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DHDG_EE_PROBE -Iinclude
-//          -Ihd-gnn_amd/csrc tools/probe/eefwd_probe.hip hd-gnn_amd/csrc/hdgnn.hip -o ...
+//          -Ihd-gnn_amd/csrc tools/probe/eefwd_probe.hip hd-gnn_amd/csrc/hdgnn.hip
+//          hd-gnn_amd/csrc/prep.hip hd-gnn_amd/csrc/dp.hip hd-gnn_amd/csrc/ckpt.cpp -o ...
 #include "../../hd-gnn_amd/csrc/wide.hip"
 #include <algorithm>
 #include <cstdio>
