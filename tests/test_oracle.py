@@ -63,9 +63,18 @@ def _rand_case(seed, B=3, ne=7, nc=5):
     return x, a, y, hid, nlen
 
 
-@pytest.mark.parametrize("seed", [0, 1, 2])
-def test_pair_explicit_equals_literal(seed):
+@pytest.mark.parametrize("seed,kind", [(0, None), (1, None), (2, None), (3, "upper"),
+                                       (4, "tournament")],
+                         ids=["0", "1", "2", "upper", "tournament"])
+def test_pair_explicit_equals_literal(seed, kind):
+    """kind: y replaced by a one-sided / anti-symmetric label draw (tests/_labels.py), whose
+    logits and gradients move by hundreds of tolerances under y -> y^T: the literal incidence
+    restatement pins the orientation of the pair-explicit oracle for those kinds too."""
     x, a, y, hid, nlen = _rand_case(seed)
+    if kind is not None:
+        from tests._labels import label_grid
+        y = label_grid(kind, y.shape[0], y.shape[1], seed).astype(y.dtype)
+        assert (y != y.transpose(0, 2, 1)).any(axis=(1, 2)).all()
     params = model_ref.init_params(seed)
     B, ne = x.shape
     nc = y.shape[1]

@@ -195,21 +195,10 @@ GUARD_EPS, GUARD_DRAWS, GUARD_FRACTION, LOGIT_MAX = 2e-7, 3, 0.5, 1e4
 CE_RTOL = 1e-5          # the GPU cases' relative CE tolerance
 
 
-@pytest.mark.parametrize("entry", R.oracle_entries(),
-                         ids=lambda e: "%s-v%d-%dx%dx%d" % e[:5])
-def test_table_entry_is_well_conditioned(entry):
-    """Kink guard: the oracle's own gradient at theta and at theta (1 + 2e-7 s), three sign
-    draws s, differ by at most half the tolerance the entry's GPU cases are held to -- a relu
-    crossing within fp32 rounding of the parameters moves it by more than the whole tolerance,
-    and then a mismatch says nothing about a kernel.  Logit range: max |logit| <= 1e4, the
-    range the tolerances were set for.  CE condition: the oracle run in float32 gives the
-    float64 CE to half the relative tolerance of the GPU check -- when the labels are
-    separated completely CE falls to 1e-4 or to 0 and a relative check of it in fp32 measures
-    nothing.  An entry that fails moves to the next seed in _regimes.MOVED; it is never
-    waived."""
-    reg, v, B, ne, nc, dseed, pseed, fused = entry
-    cb = synth_commits(B, ne, nc, dseed)
-    flat = R.regime_flat(reg, pseed, v, data=cb)
+def check_well_conditioned(flat, cb, v, fused):
+    """The three guards of test_table_entry_is_well_conditioned on one (parameters, batch);
+    -> the float64 oracle's (out, flat gradient).  tests/test_labels.py applies them to its
+    own table."""
     out, g0 = _oracle_grad(flat, cb, v)
     assert np.isfinite(g0).all()
     assert np.abs(out["logits"]).max() <= LOGIT_MAX
@@ -226,3 +215,22 @@ def test_table_entry_is_well_conditioned(entry):
             worst = max(worst, frac)
             assert frac <= GUARD_FRACTION, "%s: %.3g of the tolerance" % (name, frac)
     print("guard %.3g of tol, max|logit| %.4g" % (worst, np.abs(out["logits"]).max()))
+    return out, g0
+
+
+@pytest.mark.parametrize("entry", R.oracle_entries(),
+                         ids=lambda e: "%s-v%d-%dx%dx%d" % e[:5])
+def test_table_entry_is_well_conditioned(entry):
+    """Kink guard: the oracle's own gradient at theta and at theta (1 + 2e-7 s), three sign
+    draws s, differ by at most half the tolerance the entry's GPU cases are held to -- a relu
+    crossing within fp32 rounding of the parameters moves it by more than the whole tolerance,
+    and then a mismatch says nothing about a kernel.  Logit range: max |logit| <= 1e4, the
+    range the tolerances were set for.  CE condition: the oracle run in float32 gives the
+    float64 CE to half the relative tolerance of the GPU check -- when the labels are
+    separated completely CE falls to 1e-4 or to 0 and a relative check of it in fp32 measures
+    nothing.  An entry that fails moves to the next seed in _regimes.MOVED; it is never
+    waived."""
+    reg, v, B, ne, nc, dseed, pseed, fused = entry
+    cb = synth_commits(B, ne, nc, dseed)
+    flat = R.regime_flat(reg, pseed, v, data=cb)
+    check_well_conditioned(flat, cb, v, fused)
