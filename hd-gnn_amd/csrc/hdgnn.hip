@@ -929,13 +929,16 @@ __device__ __forceinline__ f4v mfma_tile16(FA fa, FB fb, const int K, const int 
     c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c1, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c0, 0, 0, 0);
     c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c1, 0, 0, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // pinned: 8 DS reads, then 4 MFMAs
+    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);   // (xlane.h, mfma_tile16_p<BATCH>)
   }
   for (; k < K; k += 4)
     c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa(r, k + q), fb(k + q, r), c0, 0, 0, 0);
   return c0 + c1;
 }
 
-// mfma_tile16_p (strided operands): hdgnn_internal.h, shared with the general path
+// mfma_tile16_p (strided operands): xlane.h, shared with the general path; the step kernel
+// takes its BATCH form
 
 // Two 16x16 tiles sharing the A rows (the two 16-column halves of a 20-wide output):
 // one A read per k step feeds both MFMAs, the two accumulation chains interleave.
@@ -949,21 +952,37 @@ __device__ __forceinline__ void mfma_tile16x2_p(const float* pa, const int sa, c
   f4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
   int k = 0;
   for (; k + 16 <= K; k += 16) {
-    float av[4], bv0[4], bv1[4];
+    float av[5], bv0[5], bv1[5];
+    // the 4-step that follows the last body (K = 20: the node chains) rides with it: its
+    // three reads are issued with the body's twelve, its MFMAs close the same two chains
+    const bool t4 = k + 32 > K && k + 20 <= K;
+    const int nu = t4 ? 5 : 4;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      av[u] = a[4 * u * sa];
-      bv0[u] = b0[4 * u * sb0];
-      bv1[u] = b1[4 * u * sb1];
+    for (int u = 0; u < 5; ++u) {
+      if (u < nu) {
+        av[u] = a[4 * u * sa];
+        bv0[u] = b0[4 * u * sb0];
+        bv1[u] = b1[4 * u * sb1];
+      }
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv0[u], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv1[u], c1, 0, 0, 0);
+    for (int u = 0; u < 5; ++u) {
+      if (u < nu) {
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv0[u], c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv1[u], c1, 0, 0, 0);
+      }
     }
-    a += 16 * sa;
-    b0 += 16 * sb0;
-    b1 += 16 * sb1;
+    if (t4) {                          // K is a constant at every call site: one arm remains
+      __builtin_amdgcn_sched_group_barrier(0x100, 15, 0);   // pinned: all DS reads,
+      __builtin_amdgcn_sched_group_barrier(0x008, 10, 0);   // then the MFMAs
+    } else {
+      __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+    }
+    a += 4 * nu * sa;
+    b0 += 4 * nu * sb0;
+    b1 += 4 * nu * sb1;
+    k += 4 * nu - 16;
   }
   for (; k + 4 <= K; k += 4) {
     c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b0[0], c0, 0, 0, 0);
@@ -978,6 +997,34 @@ __device__ __forceinline__ void mfma_tile16x2_p(const float* pa, const int sa, c
     c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, ok ? b0[0] : 0.f, c0, 0, 0, 0);
     c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, ok ? b1[0] : 0.f, c1, 0, 0, 0);
   }
+  o0 = c0;
+  o1 = c1;
+}
+
+// The K = HS double tile with the A fragment already in registers: av[u] is this lane's
+// A[lane & 15][4 u + (lane >> 4)].  The MFMA steps and their order are mfma_tile16x2_p's at
+// K = 20 (four body steps, then the 4-step), so the bits are too.
+__device__ __forceinline__ void mfma_tile16x2_r(const float (&av)[HS / 4], const float* pb0,
+                                                const int sb0, const float* pb1, const int sb1,
+                                                const int lane, f4v& o0, f4v& o1) {
+  static_assert(HS % 4 == 0 && HS / 4 == 5, "one 16-step body and one 4-step");
+  const int q = lane >> 4;
+  const float* b0 = pb0 + q * sb0;
+  const float* b1 = pb1 + q * sb1;
+  float bv0[HS / 4], bv1[HS / 4];
+#pragma unroll
+  for (int u = 0; u < HS / 4; ++u) {
+    bv0[u] = b0[4 * u * sb0];
+    bv1[u] = b1[4 * u * sb1];
+  }
+  f4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
+#pragma unroll
+  for (int u = 0; u < HS / 4; ++u) {
+    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv0[u], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv1[u], c1, 0, 0, 0);
+  }
+  __builtin_amdgcn_sched_group_barrier(0x100, 2 * (HS / 4), 0);   // pinned: the B reads,
+  __builtin_amdgcn_sched_group_barrier(0x008, 2 * (HS / 4), 0);   // then the MFMAs
   o0 = c0;
   o1 = c1;
 }
@@ -1616,53 +1663,70 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const int row0 = rb * 16;
     const int ir = row0 + (lane & 15);                         // this lane's A row
     const bool rv = ir >= nlo && ir < nhi;
+    // the lane's output columns m0 | m1 (m1 >= HS: a clamped address, its results unused) and
+    // rows i0 .. i0 + 3.  Everything the two epilogues read besides the tiles is fetched
+    // here, unconditionally, so neither epilogue waits on LDS inside a predicated block.
+    const int m0 = lane & 15, m1 = 16 + m0, mc[2] = {m0, min(m1, HS - 1)};
+    const bool mv[2] = {true, m1 < HS};
+    const int i0 = row0 + 4 * (lane >> 4);
+    float b5v[2], b1v[2], w0v[2], w2v[2], xv[4];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      b5v[cb] = Ws[E1_B5 + mc[cb]];
+      b1v[cb] = Ws[E3_B1 + mc[cb]];
+      w0v[cb] = Ws[E3_W1 + mc[cb]];
+      w2v[cb] = Ws[E3_W2 + mc[cb]];
+    }
+    bool own[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      own[q] = i0 + q >= nlo && i0 + q < nhi;
+      xv[q] = xs[min(max(i0 + q, nlo), nhi - 1)];              // an own row; used where own[q]
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keeps these reads out of the tile's pinned read group
     {                                  // both 16-column halves, shared A reads
       f4v cc[2];
-      const int m0 = lane & 15, m1 = 16 + (lane & 15);
       mfma_tile16x2_p(rv ? Ps + ir * HS : kzero, rv ? 1 : 0, Ws + E1_W5 + m0, HS,
-                      m1 < HS ? Ws + E1_W5 + m1 : kzero, m1 < HS ? HS : 0, HS, lane, cc[0], cc[1]);
+                      mv[1] ? Ws + E1_W5 + m1 : kzero, mv[1] ? HS : 0, HS, lane, cc[0], cc[1]);
+      float e[2][4];
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
-        const int col0 = cb * 16;
-        const f4v c = cc[cb];
-        const int m = col0 + (lane & 15);
-        if (m < HS) {
-          const float bias = twoNe1 * Ws[E1_B5 + m];
+        const float bias = twoNe1 * b5v[cb];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int i = row0 + 4 * (lane >> 4) + q;
-            if (i >= nlo && i < nhi) {
-              Eb[i * HS + m] = c[q] + bias;
-              EbG[i * HS + m] = c[q] + bias;
-            }
+        for (int q = 0; q < 4; ++q) e[cb][q] = cc[cb][q] + bias;
+      }
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (mv[cb] && own[q]) {
+            Eb[(i0 + q) * HS + mc[cb]] = e[cb][q];
+            EbG[(i0 + q) * HS + mc[cb]] = e[cb][q];
           }
         }
       }
     }
     {                                  // both 16-column halves, shared A reads
       f4v cc[2];
-      const int m0 = lane & 15, m1 = 16 + (lane & 15);
       mfma_tile16x2_p(rv ? Eb + ir * HS : kzero, rv ? 1 : 0, Ws + E3_W1 + HS + m0, HS,
-                      m1 < HS ? Ws + E3_W1 + HS + m1 : kzero, m1 < HS ? HS : 0, HS, lane, cc[0], cc[1]);
+                      mv[1] ? Ws + E3_W1 + HS + m1 : kzero, mv[1] ? HS : 0, HS, lane, cc[0], cc[1]);
       // h = relu(...) in the tile registers; o = h w2' + b2' as a 16-lane row sum of the
       // lanes' h w2' products (no LDS round trip for h)
       float ow[4] = {0.f, 0.f, 0.f, 0.f};
+      float hv[2][4];
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {   // same wave: its E_bar rows are complete (LDS in order)
-        const int col0 = cb * 16;        // [x, E_bar] W1' = E_bar W1'[1:] (MFMA) + x W1'[0]
-        const f4v c = cc[cb];
-        const int m = col0 + (lane & 15);
-        if (m < HS) {
-          const float bias = Ws[E3_B1 + m], w0 = Ws[E3_W1 + m], w2 = Ws[E3_W2 + m];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int i = row0 + 4 * (lane >> 4) + q;
-            const bool own = i >= nlo && i < nhi;
-            const float v = relu(fmaf(xs[own ? i : nlo], w0, c[q]) + bias);
-            if (own) hEG[i * HS + m] = v;
-            ow[q] = fmaf(v, w2, ow[q]);
-          }
+#pragma unroll                           // [x, E_bar] W1' = E_bar W1'[1:] (MFMA) + x W1'[0]
+        for (int q = 0; q < 4; ++q) {
+          hv[cb][q] = relu(fmaf(xv[q], w0v[cb], cc[cb][q]) + b1v[cb]);
+          ow[q] = mv[cb] ? fmaf(hv[cb][q], w2v[cb], ow[q]) : ow[q];
         }
+      }
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (mv[cb] && own[q]) hEG[(i0 + q) * HS + mc[cb]] = hv[cb][q];
       }
       row16_sums(ow);
       const int q = lane & 15, i = row0 + 4 * (lane >> 4) + q;
@@ -1848,8 +1912,8 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
       const int row0 = (tile >> 1) * 16, col0 = (tile & 1) * 16;
       const float* src = which ? Hh : G;
       const int pr = row0 + (lane & 15), mc = col0 + (lane & 15);
-      const f4v c = mfma_tile16_p(pr < Nc ? src + pr * HS : kzero, pr < Nc ? 1 : 0,
-                                  mc < HS ? Mm + mc : kzero, mc < HS ? HS : 0, HS, lane);
+      const f4v c = mfma_tile16_p<true>(pr < Nc ? src + pr * HS : kzero, pr < Nc ? 1 : 0,
+                                        mc < HS ? Mm + mc : kzero, mc < HS ? HS : 0, HS, lane);
       const int m = col0 + (lane & 15);
       if (m < HS) {
         const float off = which ? t0v[m] : s0v[m], ek = eps[m];
@@ -2130,11 +2194,11 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const int which = tile >> 2, row0 = ((tile >> 1) & 1) * 16, col0 = (tile & 1) * 16;
     const int ra = row0 + (lane & 15), cb = col0 + (lane & 15);
     const f4v c = which == 0
-        ? mfma_tile16_p(ra < HS ? Ws + H1_W2 + ra : kzero, ra < HS ? HS : 0,     // V2^T
-                        cb < HS ? Xm + cb : kzero, cb < HS ? HS : 0, HS, lane)    // X
-        : mfma_tile16_p(ra < HS ? Xm + ra * HS : kzero, ra < HS ? 1 : 0,          // X
-                        cb < HS ? Ws + H2_W1 + (2 + cb) * HS : kzero, cb < HS ? 1 : 0,
-                        HS, lane);                                                  // U1e^T
+        ? mfma_tile16_p<true>(ra < HS ? Ws + H1_W2 + ra : kzero, ra < HS ? HS : 0,     // V2^T
+                              cb < HS ? Xm + cb : kzero, cb < HS ? HS : 0, HS, lane)    // X
+        : mfma_tile16_p<true>(ra < HS ? Xm + ra * HS : kzero, ra < HS ? 1 : 0,          // X
+                              cb < HS ? Ws + H2_W1 + (2 + cb) * HS : kzero, cb < HS ? 1 : 0,
+                              HS, lane);                                                  // U1e^T
     const int cc = col0 + (lane & 15);
     if (cc < HS) {
       const float sdt = sumD[cc] + red[cc];
@@ -2162,8 +2226,8 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const int row0 = (rc >> 1) * 16, col0 = (rc & 1) * 16;
     const float* src = which ? Dtau : Dsig;
     const int pr = row0 + (lane & 15), lc = col0 + (lane & 15);
-    const f4v c = mfma_tile16_p(pr < Nc ? src + pr * HS : kzero, pr < Nc ? 1 : 0,
-                                lc < HS ? Mcm + lc * HS : kzero, lc < HS ? 1 : 0, HS, lane);
+    const f4v c = mfma_tile16_p<true>(pr < Nc ? src + pr * HS : kzero, pr < Nc ? 1 : 0,
+                                      lc < HS ? Mcm + lc * HS : kzero, lc < HS ? 1 : 0, HS, lane);
     const int l = col0 + (lane & 15);
     if (l < HS) {
       float* dst = which ? dH : dG;
@@ -2240,10 +2304,10 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   if (wv < SMAXC) {   // MFMA row tiles
     const int row0 = wv * 16, rr = row0 + (lane & 15), m = lane & 15;
     const bool rv = rr < Nc, mv = m < ndm;
-    const f4v c = mfma_tile16_p(rv ? Dal + rr * HS : kzero, rv ? 1 : 0,
-                                mv ? Ws + H1_W1 + m * HS : kzero, mv ? 1 : 0, HS, lane) +
-                  mfma_tile16_p(rv ? Dbe + rr * HS : kzero, rv ? 1 : 0,
-                                mv ? Ws + H1_W1 + (4 + m) * HS : kzero, mv ? 1 : 0, HS, lane);
+    const f4v c = mfma_tile16_p<true>(rv ? Dal + rr * HS : kzero, rv ? 1 : 0,
+                                      mv ? Ws + H1_W1 + m * HS : kzero, mv ? 1 : 0, HS, lane) +
+                  mfma_tile16_p<true>(rv ? Dbe + rr * HS : kzero, rv ? 1 : 0,
+                                      mv ? Ws + H1_W1 + (4 + m) * HS : kzero, mv ? 1 : 0, HS, lane);
     if (mv) {
       float* dst = m < 2 ? dnb + m : dnc + (m - 2);
 #pragma unroll
@@ -2285,8 +2349,8 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const float* D = side ? Dbe : Dal;
     const int r = lane & 15, mc = col0 + (lane & 15);
     const float* pa = r < 4 ? nb + r : ((r == 4 && side == 0) ? kone : kzero);
-    const f4v c = mfma_tile16_p(pa, r < 4 ? 4 : 0, mc < HS ? D + mc : kzero, mc < HS ? HS : 0, Nc,
-                                lane);
+    const f4v c = mfma_tile16_p<true>(pa, r < 4 ? 4 : 0, mc < HS ? D + mc : kzero,
+                                      mc < HS ? HS : 0, Nc, lane);
     const int m = col0 + (lane & 15);
     if (m < HS) {
       if (lane < 16) {
@@ -2410,19 +2474,45 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   // rho = dE W5^T (into h's rows, consumed first); partial dw2' / db2' of the block
   for (int rb = (nlo >> 4) + wv; rb <= ((nhi - 1) >> 4); rb += NT_MID / 64) {   // wave-uniform
     const int row0 = rb * 16;
-    for (int e = lane; e < 16 * HS; e += 64) {
-      const int i = row0 + e / HS, k = e - (e / HS) * HS;
-      if (i >= nlo && i < nhi) dq[i * HS + k] = (hB[i * HS + k] > 0.f) ? Ws[E3_W2 + k] * dxp[i] : 0.f;
+    const int ir = row0 + (lane & 15);
+    const bool rv = ir >= nlo && ir < nhi;
+    // this lane's A fragment of dq: dq[ir][4 u + (lane >> 4)], the five k steps of the dE
+    // tile, straight from h, w2' and do (clamped row, loads unconditional and together, as
+    // pair_tile does); it feeds the MFMAs from registers and goes to the dq slot for M13
+    // in passing, so no LDS write -> read stands before the first tile
+    float dqa[5];
+    {
+      const int irc = min(max(ir, nlo), nhi - 1), kq = lane >> 4;   // an own row
+      const float d = dxp[irc];
+      float hv[5], wq[5];
+#pragma unroll
+      for (int u = 0; u < 5; ++u) {
+        hv[u] = hB[irc * HS + 4 * u + kq];
+        wq[u] = Ws[E3_W2 + 4 * u + kq];
+      }
+#pragma unroll
+      for (int u = 0; u < 5; ++u) {
+        const float v = (hv[u] > 0.f) ? wq[u] * d : 0.f;
+        dqa[u] = rv ? v : 0.f;
+      }
+      if (rv) {
+#pragma unroll
+        for (int u = 0; u < 5; ++u) dq[ir * HS + 4 * u + kq] = dqa[u];
+      }
     }
     {   // dw2' / db2' partials of the block: lane = (row r = lane / 4, units k = kq + 4 j)
       const int r = lane >> 2, kq = lane & 3, i = row0 + r;
       const bool ok = i >= nlo && i < nhi;
-      const float d = ok ? dxp[i] : 0.f;
+      const int ic = min(max(i, nlo), nhi - 1);
+      const float dl = dxp[ic], d = ok ? dl : 0.f;
+      float hv[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) hv[j] = hB[ic * HS + min(kq + 4 * j, HS - 1)];
       float v[6];
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         const int k = kq + 4 * j;
-        v[j] = (ok && k < HS) ? hB[i * HS + k] * d : (k == HS ? d : 0.f);
+        v[j] = (ok && k < HS) ? hv[j] * d : (k == HS ? d : 0.f);
       }
 #pragma unroll
       for (int j = 0; j < 6; ++j) {                 // sum over the 16 rows (lane bits 2..5):
@@ -2436,13 +2526,11 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
           if (kq + 4 * j <= HS) dw2p[rb * 21 + kq + 4 * j] = v[j];
       }
     }
-    const int ir = row0 + (lane & 15);
-    const bool rv = ir >= nlo && ir < nhi;
-    {                                  // both 16-column halves, shared A reads
+    {                                  // both 16-column halves, shared A operand
       f4v cc[2];
       const int m0 = lane & 15, m1 = 16 + (lane & 15);
-      mfma_tile16x2_p(rv ? dq + ir * HS : kzero, rv ? 1 : 0, Ws + E3_W1 + (1 + m0) * HS, 1,
-                      m1 < HS ? Ws + E3_W1 + (1 + m1) * HS : kzero, m1 < HS ? 1 : 0, HS, lane, cc[0], cc[1]);
+      mfma_tile16x2_r(dqa, Ws + E3_W1 + (1 + m0) * HS, 1,
+                      m1 < HS ? Ws + E3_W1 + (1 + m1) * HS : kzero, m1 < HS ? 1 : 0, lane, cc[0], cc[1]);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
         const int col0 = cb * 16;
@@ -2492,8 +2580,8 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const int lr = row0 + (lane & 15), kc = col0 + (lane & 15);
     const float* pa = lr == 0 ? xs : (lr <= HS ? Eb + lr - 1 : (lr == HS + 1 ? kone : kzero));
     const int sa = lr == 0 ? 1 : (lr <= HS ? HS : 0);
-    const f4v c = mfma_tile16_p(pa + nlo * sa, sa, kc < HS ? dq + kc + nlo * HS : kzero,
-                                kc < HS ? HS : 0, nhi - nlo, lane);
+    const f4v c = mfma_tile16_p<true>(pa + nlo * sa, sa, kc < HS ? dq + kc + nlo * HS : kzero,
+                                      kc < HS ? HS : 0, nhi - nlo, lane);
     const int k = col0 + (lane & 15);
     if (k < HS) {
 #pragma unroll
@@ -2506,9 +2594,9 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   } else if (wv < 8) {
     const int row0 = ((wv - 4) >> 1) * 16, col0 = ((wv - 4) & 1) * 16;
     const int lr = row0 + (lane & 15), kc = col0 + (lane & 15);
-    const f4v c = mfma_tile16_p(lr < HS ? Ps + lr + nlo * HS : (lr == HS ? kone : kzero),
-                                lr < HS ? HS : 0, kc < HS ? dE + kc + nlo * HS : kzero,
-                                kc < HS ? HS : 0, nhi - nlo, lane);
+    const f4v c = mfma_tile16_p<true>(lr < HS ? Ps + lr + nlo * HS : (lr == HS ? kone : kzero),
+                                      lr < HS ? HS : 0, kc < HS ? dE + kc + nlo * HS : kzero,
+                                      kc < HS ? HS : 0, nhi - nlo, lane);
     const int k = col0 + (lane & 15);
     if (k < HS) {
 #pragma unroll

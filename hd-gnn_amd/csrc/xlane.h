@@ -86,6 +86,12 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // pa[k * sa] and column r of B as pb[k * sb], k < K.  A row / column outside the matrix
 // passes a pointer to a 0.f word with stride 0 (a row of ones: a 1.f word, stride 0), so
 // the K loop carries no bounds logic: one LDS read and one address add per operand.
+// BATCH pins the 16-step body's schedule to its source order: the eight operand reads, then
+// the four MFMAs (each behind the partial wait its own pair needs).  Without it the scheduler
+// interleaves read, wait, MFMA under register pressure: one LDS round trip per k step.  Same
+// operands in the same steps either way; the fused step kernel asks for it, the general
+// path keeps the scheduler's choice.
+template <bool BATCH = false>
 __device__ __forceinline__ f4v mfma_tile16_p(const float* pa, const int sa, const float* pb,
                                              const int sb, const int K, const int lane) {
   const int q = lane >> 4;
@@ -105,6 +111,10 @@ __device__ __forceinline__ f4v mfma_tile16_p(const float* pa, const int sa, cons
     c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], c1, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], c0, 0, 0, 0);
     c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], c1, 0, 0, 0);
+    if constexpr (BATCH) {
+      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // 8 DS reads
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);   // then 4 MFMAs
+    }
     a += 4 * sa4;
     b += 4 * sb4;
   }
