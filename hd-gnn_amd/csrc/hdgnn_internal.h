@@ -9,6 +9,7 @@
 //   batch prep   prep.hip   the parameter-independent tables of an uploaded batch
 //   dp tail      dp.hip     the data-parallel tail over xGMI and its mailbox API
 //   evaluation   eval.hip   on-device confusion counts and ROC-AUC
+//   untangling   untangle.hip  on-device hunk groups and partition pair counts
 //   host only    ckpt.cpp   CRC-32C and the checkpoint bundle writer (err.h alone)
 //
 //   xlane.h       cross-lane / packed-math device primitives of every path

@@ -62,6 +62,18 @@ STATUS_XCH_TIMEOUT, STATUS_DP_TIMEOUT = 1, 2
 # hdg_eval's per-commit table (include/hdgnn.h): ev[B][EV_SLOTS] u64
 EV_SLOTS, EV_TP, EV_FP, EV_FN, EV_TN, EV_U2, EV_NAN = 8, 0, 1, 2, 3, 4, 5
 EVAL_CHUNK = 16384     # relations per block of the evaluation kernel
+# hdg_untangle's per-commit table (include/hdgnn.h): ut[B][UT_SLOTS] u64
+UT_SLOTS = 8
+UT_GROUPS, UT_TGROUPS, UT_SS, UT_SD, UT_DS, UT_DD, UT_LINKS, UT_NAN = range(8)
+UT_RULE_MEAN, UT_RULE_ANY, UT_RULE_BOTH = 0, 1, 2
+UT_RULES = {"mean": UT_RULE_MEAN, "any": UT_RULE_ANY, "both": UT_RULE_BOTH}
+UT_TILE, UT_TILES_PER_BLOCK, UT_MAX_BLOCKS = 64, 4, 16
+
+
+def untangle_blocks(nc):
+    """Blocks per commit of hdg_untangle's link kernel (a function of nc alone)."""
+    t = -(-nc // UT_TILE)
+    return min(-(-(t * (t + 1) // 2) // UT_TILES_PER_BLOCK), UT_MAX_BLOCKS)
 
 
 def trailer_count(tr):
@@ -80,7 +92,7 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_bundle_write", "hdg_ckpt_writer_create", "hdg_ckpt_writer_submit",
            "hdg_ckpt_writer_flush", "hdg_ckpt_writer_poll", "hdg_ckpt_writer_destroy", "hdg_memcpy_async",
            "hdg_event_create", "hdg_event_record", "hdg_event_synchronize", "hdg_event_destroy",
-           "hdg_eval"]
+           "hdg_eval", "hdg_untangle_workspace_bytes", "hdg_untangle"]
 
 _lib = None
 
@@ -120,6 +132,9 @@ def load(path=None):
     lib.hdg_train_step.argtypes = [P(Shape), P(Batch), P(State), f32, P(Outputs), vp, vp, vp]
     lib.hdg_forward.argtypes = [P(Shape), P(Batch), vp, P(Outputs), vp, vp, vp]
     lib.hdg_eval.argtypes = [P(Shape), P(Batch), vp, vp, vp]
+    lib.hdg_untangle_workspace_bytes.argtypes = [P(Shape)]
+    lib.hdg_untangle_workspace_bytes.restype = ctypes.c_size_t
+    lib.hdg_untangle.argtypes = [P(Shape), P(Batch), vp, f32, i32, vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

@@ -384,3 +384,38 @@ class Engine:
                                      ctypes.c_void_p(probs.data_ptr()),
                                      ctypes.c_void_p(ev.data_ptr()), self._stream()))
         return ev
+
+    def untangle(self, dbatch, probs=None, threshold=0.5, rule="mean"):
+        """hdg_untangle: the hunk groups `probs` ([B][2][nc(nc-1)] fp32 on this device; default
+        self.probs as the last forward / fwd_bwd / train step left it) gives under the link
+        rule ("mean" | "any" | "both" against `threshold`, strict comparisons; include/hdgnn.h)
+        and their pair counts against the batch's true groups -> (groups int32 [B][nc], ut
+        int64 [B][UT_SLOTS]) as fresh device tensors (hdgnn.metrics.scores_from_untangle turns
+        ut into scores).  Enqueued on the current stream; nothing is copied to the host.  The
+        workspace is allocated on the first call and kept."""
+        self._check(dbatch)
+        probs = self.probs if probs is None else probs
+        if (probs.device != self.device or probs.dtype != torch.float32
+                or not probs.is_contiguous()
+                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
+            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
+                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        if rule not in _lib.UT_RULES:
+            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        if getattr(self, "_ut_workspace", None) is None:
+            nbytes = self.lib.hdg_untangle_workspace_bytes(ctypes.byref(self.shape))
+            if nbytes == 0:
+                raise RuntimeError(self.lib.hdg_last_error().decode())
+            self._ut_workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.device)
+        groups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
+        # u64 counts, every value < 2^63: int64 reads them as they are
+        ut = torch.empty(self.batch, _lib.UT_SLOTS, dtype=torch.int64, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_untangle(ctypes.byref(self.shape), ctypes.byref(b),
+                                         ctypes.c_void_p(probs.data_ptr()),
+                                         ctypes.c_float(threshold), _lib.UT_RULES[rule],
+                                         ctypes.c_void_p(groups.data_ptr()), None,
+                                         ctypes.c_void_p(ut.data_ptr()),
+                                         ctypes.c_void_p(self._ut_workspace.data_ptr()),
+                                         self._stream()))
+        return groups, ut

@@ -161,3 +161,114 @@ def scores_from_counts(ev):
     out["auc_commits"] = int(both.sum())
     out["nan_relations"] = int(ev[:, EV_NAN].sum())
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# Untangling: the hunk groups a threshold on the pair scores gives (connected components of
+# the link graph) against the true groups (components of the label graph), as the integer
+# table hdg_untangle computes on the device (include/hdgnn.h, HDG_UT_*), its host
+# implementation, and the partition scores that follow from it.
+# ---------------------------------------------------------------------------------------
+UT_SLOTS = 8
+UT_GROUPS, UT_TGROUPS, UT_SS, UT_SD, UT_DS, UT_DD, UT_LINKS, UT_NAN = range(8)
+UT_RULES = ("mean", "any", "both")
+
+
+def _components(n, a, b):
+    """Connected components of the undirected edges (a[k], b[k]) on nodes 0..n-1 -> int32 (n,)
+    dense ids ordered by each component's smallest member.  Min-label propagation over the
+    edge list with one pointer jump per round, until a fixed point: then every node carries
+    its component's smallest member, and the id of a component is the number of smaller ones."""
+    lab = np.arange(n, dtype=np.int64)
+    while a.size:
+        new = lab.copy()
+        m = np.minimum(lab[a], lab[b])
+        np.minimum.at(new, a, m)
+        np.minimum.at(new, b, m)
+        new = new[new]
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    ids = np.cumsum(lab == np.arange(n)) - 1
+    return ids[lab].astype(np.int32)
+
+
+def untangle_counts(label_onehot, probs, threshold=0.5, rule="mean"):
+    """(B, 2, R) one-hot labels and probabilities, R = Nc (Nc - 1) -> (ut int64 (B, UT_SLOTS),
+    groups int32 (B, Nc), tgroups int32 (B, Nc)): the host implementation of hdg_untangle,
+    definitions as in include/hdgnn.h.  With s_pq = probs[b, 1, r(p, q)] in float32, the pair
+    {p, q} is linked iff  mean: s_pq + s_qp > threshold + threshold (both sums in float32),
+    any: s_pq > threshold or s_qp > threshold,  both: and  -- strict comparisons, and never
+    when either score is NaN (such pairs count in UT_NAN).  groups: components of the link
+    graph; tgroups: components of y_pq | y_qp; ids dense, ordered by smallest member."""
+    from .data import pair_index
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    thr = np.float32(threshold)
+    if np.isnan(thr):
+        raise ValueError("threshold is NaN")
+    label = np.asarray(label_onehot)
+    probs = np.asarray(probs, np.float32)
+    B, R = probs.shape[0], probs.shape[2]
+    nc = int(round((1.0 + np.sqrt(1.0 + 4.0 * R)) / 2.0))
+    if nc < 2 or nc * (nc - 1) != R:
+        raise ValueError("R = %d is not Nc (Nc - 1)" % R)
+    I, J = pair_index(nc)
+    iu, ju = np.triu_indices(nc, 1)
+    ut = np.zeros((B, UT_SLOTS), np.int64)
+    groups = np.zeros((B, nc), np.int32)
+    tgroups = np.zeros((B, nc), np.int32)
+    S = np.zeros((nc, nc), np.float32)
+    Y = np.zeros((nc, nc), bool)
+    for b in range(B):
+        S[I, J] = probs[b, 1]
+        Y[I, J] = label[b, 1] > label[b, 0]
+        spq, sqp = S[iu, ju], S[ju, iu]
+        nan = np.isnan(spq) | np.isnan(sqp)
+        with np.errstate(invalid="ignore", over="ignore"):
+            if rule == "mean":
+                link = (spq + sqp) > (thr + thr)
+            elif rule == "any":
+                link = (spq > thr) | (sqp > thr)
+            else:
+                link = (spq > thr) & (sqp > thr)
+        link &= ~nan
+        ylink = Y[iu, ju] | Y[ju, iu]
+        g = _components(nc, iu[link], ju[link])
+        t = _components(nc, iu[ylink], ju[ylink])
+        sp, st = g[iu] == g[ju], t[iu] == t[ju]
+        groups[b], tgroups[b] = g, t
+        ut[b] = (int(g.max()) + 1, int(t.max()) + 1, np.count_nonzero(sp & st),
+                 np.count_nonzero(sp & ~st), np.count_nonzero(~sp & st),
+                 np.count_nonzero(~sp & ~st), np.count_nonzero(link), np.count_nonzero(nan))
+    return ut, groups, tgroups
+
+
+def scores_from_untangle(ut):
+    """(n_commits, UT_SLOTS) integer table -> dict of partition scores.
+
+    rand = (SS + DD) / all pairs, precision = SS / (SS + SD), recall = SS / (SS + DS),
+    f1 = 2 SS / (2 SS + SD + DS): pooled over the pairs of all commits; rand_mean /
+    precision_mean / recall_mean / f1_mean: the mean of the per-commit ratios over the commits
+    where the ratio is defined.  A ratio with a zero denominator is nan (scores_from_counts'
+    rule).  exact: share of commits whose predicted partition is the true one (SD = DS = 0);
+    group_count_match: share with as many predicted as true groups (both nan without
+    commits); nan_pairs: pairs never linked because a score was NaN."""
+    ut = np.asarray(ut).reshape(-1, UT_SLOTS).astype(np.int64)
+    ss, sd, ds, dd = (ut[:, k] for k in (UT_SS, UT_SD, UT_DS, UT_DD))
+
+    def four(ss, sd, ds, dd):
+        return (_ratio(ss + dd, ss + sd + ds + dd), _ratio(ss, ss + sd), _ratio(ss, ss + ds),
+                _ratio(2 * ss, 2 * ss + sd + ds))
+
+    out = {}
+    for n, pooled, per in zip(("rand", "precision", "recall", "f1"),
+                              four(ss.sum(), sd.sum(), ds.sum(), dd.sum()), four(ss, sd, ds, dd)):
+        out[n] = float(pooled)
+        out[n + "_mean"] = _nanmean(per)
+    n = len(ut)
+    out["exact"] = float(((sd == 0) & (ds == 0)).mean()) if n else float("nan")
+    out["group_count_match"] = (float((ut[:, UT_GROUPS] == ut[:, UT_TGROUPS]).mean()) if n
+                                else float("nan"))
+    out["nan_pairs"] = int(ut[:, UT_NAN].sum())
+    return out

@@ -598,6 +598,58 @@ class graph2graph(object):
             print('eval nan relations: %d' % scores["nan_relations"])
         return scores, table
 
+    # ------------------------------------------------------------------ untangle
+    def untangle(self, args, part="test", threshold=0.5, rule="mean"):
+        """Untangle the commits of the test (or train) split with the trained classifier: per
+        batch Engine.forward then Engine.untangle (hdg_untangle), so only each commit's hunk
+        group ids and its integer row (include/hdgnn.h, HDG_UT_*) come to the host, never the
+        probabilities.  Not a reference flow (the reference stops at the pair scores).  As
+        evaluate(): the checkpoint from where train() saves it, the batches of test().
+        -> (scores dict, int64 table [n_commits][8], int32 groups [n_commits][Nc]); rank 0
+        prints the scores (metrics.scores_from_untangle) and writes untangle_groups<Ne>.npy
+        and untangle_counts<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/."""
+        import torch
+        if part not in ("train", "test"):
+            raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
+        _, _, train, test, maps = self._compact()
+        if self.load(self.checkpoint_dir):
+            print(" [*] Load SUCCESS")
+        else:
+            print(" [!] Load failed...")
+        eng = self.engine
+        rows, ids = [], []
+        for db in self._device_batches(train if part == "train" else test, maps):
+            eng.forward(db)
+            g, ut = eng.untangle(db, threshold=threshold, rule=rule)
+            ids.append(g)
+            rows.append(ut)
+        nb, lb = len(rows), self.local_batch
+        table = (torch.stack(rows).cpu().numpy() if nb
+                 else np.zeros((0, lb, _lib.UT_SLOTS), np.int64))
+        groups = (torch.stack(ids).cpu().numpy() if nb else np.zeros((0, lb, self.Nc), np.int32))
+        eng.check_status()
+        if self.world > 1 and nb:      # rank-major (W nb, lb, ..) -> batch-major commit order
+            table = self._gather(table).reshape(self.world, nb, lb, _lib.UT_SLOTS)
+            table = table.transpose(1, 0, 2, 3)
+            groups = self._gather(groups).reshape(self.world, nb, lb, self.Nc)
+            groups = groups.transpose(1, 0, 2, 3)
+        table = np.ascontiguousarray(table.reshape(-1, _lib.UT_SLOTS)).astype(np.int64)
+        groups = np.ascontiguousarray(groups.reshape(-1, self.Nc)).astype(np.int32)
+        scores = metrics.scores_from_untangle(table)
+        if self.rank == 0:
+            step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
+            os.makedirs(step_dir, exist_ok=True)
+            np.save(step_dir + 'untangle_groups' + str(self.Ne) + '.npy', groups)
+            np.save(step_dir + 'untangle_counts' + str(self.Ne) + '.npy', table)
+            print('untangle rule: %s, threshold %s' % (rule, threshold))
+            for name in ("rand", "precision", "recall", "f1"):
+                print('untangle %s: %s (per-commit mean %s)' % (name, scores[name],
+                                                                scores[name + "_mean"]))
+            print('untangle exact partitions: %s, group count match: %s (%d commits)'
+                  % (scores["exact"], scores["group_count_match"], len(table)))
+            print('untangle nan pairs: %d' % scores["nan_pairs"])
+        return scores, table, groups
+
     # ------------------------------------------------------------------ test
     def test(self, args):
         _, C_edge_test, _, test, maps = self._compact()

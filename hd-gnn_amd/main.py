@@ -8,6 +8,8 @@ MI355X instead of a TF1 session.
         hd-gnn_amd/main.py --Type train          # data parallel over N GPUs (RCCL)
     python hd-gnn_amd/main.py --Type eval      # accuracy / precision / recall / F1 / ROC-AUC
                                                # of the trained model, computed on the device
+    python hd-gnn_amd/main.py --Type untangle [--link-threshold 0.5 --link-rule mean]
+                                               # hunk groups per commit and partition scores
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -33,12 +35,16 @@ def _variant(argv):
     """Additions to the reference's flags (every reference flag is unchanged):
     --model N (1..4, default 2 = the reference main.py's `from model_2 import`): which
     model_N.graph2graph to run; --loader utils2|fast: the reference's read_data (default)
-    or hdgnn.loader reading the same dataset files straight into the compact form."""
+    or hdgnn.loader reading the same dataset files straight into the compact form;
+    --link-threshold T (default 0.5) and --link-rule mean|any|both (default mean): how
+    --Type untangle turns pair scores into links (include/hdgnn.h, hdg_untangle)."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
+    p.add_argument('--link-threshold', type=float, default=0.5)
+    p.add_argument('--link-rule', default='mean', choices=('mean', 'any', 'both'))
     a, rest = p.parse_known_args(argv)
-    return a.model, a.loader, rest
+    return a, rest
 
 
 # the reference's per-step tables (main.py:11-15): glide steps 2, 3, 5
@@ -76,7 +82,8 @@ def main(argv=None, model_cls=None):
     """model_cls: the graph2graph class to run (tests inject a recorder); default
     hdgnn.model[_N].graph2graph for --model N."""
     import importlib
-    variant, loader, argv = _variant(sys.argv[1:] if argv is None else argv)
+    extra, argv = _variant(sys.argv[1:] if argv is None else argv)
+    variant, loader = extra.model, extra.loader
     graph2graph = model_cls or importlib.import_module(
         "hdgnn.model" + ("" if variant == 2 else "_%d" % variant)).graph2graph
     if model_cls is None:
@@ -107,6 +114,8 @@ def main(argv=None, model_cls=None):
             model.test(args)
         if args.Type == 'eval':      # not in the reference: on-device scores of the trained model
             model.evaluate(args)
+        if args.Type == 'untangle':  # not in the reference: hunk groups per commit, on the device
+            model.untangle(args, threshold=extra.link_threshold, rule=extra.link_rule)
 
 
 if __name__ == '__main__':

@@ -264,6 +264,70 @@ int hdg_eval(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
              uint64_t* ev /* [batch][HDG_EV_SLOTS] */, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * On-device untangling (csrc/untangle.hip): from the same probabilities, per commit, WHICH
+ * hunks belong together -- the groups the model is for (--Step is "the number of
+ * commits/groups") -- and how well that partition matches the true one.  Not a reference
+ * flow: the reference stops at the pair scores.
+ *
+ *   score    of the directed relation (p, q), p != q: s_pq = probs[b][1][r(p, q)] with
+ *            r(p, q) = p (nc-1) + q - [q > p] (hdg_eval's layout); channel 0 is not read
+ *   link     the unordered pair {p, q} is linked iff, by `rule`,
+ *              HDG_UT_RULE_MEAN  fl32(s_pq + s_qp) > fl32(threshold + threshold)
+ *                                (the right side once on the host; fp32 addition commutes, so
+ *                                the rule is symmetric bit for bit, and nothing is multiplied)
+ *              HDG_UT_RULE_ANY   s_pq > threshold || s_qp > threshold
+ *              HDG_UT_RULE_BOTH  s_pq > threshold && s_qp > threshold
+ *            every comparison is strict (a score equal to the threshold does not link).  A
+ *            pair with a NaN in either direction is never linked and counts in HDG_UT_NAN,
+ *            under every rule
+ *   groups   predicted groups = connected components of the link graph; true groups =
+ *            connected components of the label graph y_pq | y_qp from batch->ybits (bit j of
+ *            row i; bits at j >= nc or j == i are not relations and are ignored, as hdg_eval)
+ *   ids      dense, 0 .. G-1, ordered by each group's smallest member: the id of a group is
+ *            the number of groups whose smallest member is smaller, so hunk 0 is always in
+ *            group 0 and the output is unique (device and host compare for equality).
+ *            Padded hunks are ordinary nodes: singletons on both sides
+ *   groups   [batch][nc] i32 predicted id per hunk; tgroups the true ids, or NULL
+ *   ut       [batch][HDG_UT_SLOTS] u64, every slot written by the call (nothing to zero)
+ *   workspace  hdg_untangle_workspace_bytes(shape) bytes; its content before the call does
+ *            not matter
+ * Two launches on `stream` (k_ut_link: a commit's blocks sweep 64 x 64 tiles of the
+ * pair grid into block-local union-find forests; k_ut_close: one block per commit merges
+ * them, labels both partitions and counts the pairs), no host synchronisation, no block
+ * waits for another, integer results: the same bits on every run.  Blocks per commit depend
+ * on nc alone: T = ceil(nc / 64) tile rows, T (T + 1) / 2 tile pairs I <= J,
+ * min(ceil(pairs / HDG_UT_TILES_PER_BLOCK), HDG_UT_MAX_BLOCKS) blocks, tile pair k (row-major
+ * over I <= J) on block k mod blocks.  Only shape->batch and shape->nc are used, and of the
+ * batch only ybits.  HDG_EINVAL (message in hdg_last_error) for batch outside [1, 65535], nc
+ * outside [2, 2048], an unknown rule, a NaN threshold, or a NULL probs, groups, ut,
+ * workspace or ybits.                                                                   */
+#define HDG_UT_SLOTS 8
+#define HDG_UT_GROUPS 0    /* number of predicted groups                                 */
+#define HDG_UT_TGROUPS 1   /* number of true groups                                      */
+#define HDG_UT_SS 2        /* unordered pairs p < q in the same predicted group and the
+                              same true group                                            */
+#define HDG_UT_SD 3        /* same predicted group, different true groups                */
+#define HDG_UT_DS 4        /* different predicted groups, same true group                */
+#define HDG_UT_DD 5        /* different in both: SS + SD + DS + DD = nc (nc-1) / 2       */
+#define HDG_UT_LINKS 6     /* linked unordered pairs                                     */
+#define HDG_UT_NAN 7       /* unordered pairs with a NaN score in either direction       */
+#define HDG_UT_RULE_MEAN 0
+#define HDG_UT_RULE_ANY 1
+#define HDG_UT_RULE_BOTH 2
+#define HDG_UT_TILE 64             /* hunks per tile side                                */
+#define HDG_UT_TILES_PER_BLOCK 4   /* tile pairs a block takes before a commit gets more
+                                      blocks                                             */
+#define HDG_UT_MAX_BLOCKS 16       /* ... up to this many per commit                     */
+
+size_t hdg_untangle_workspace_bytes(const hdg_shape* shape);   /* 0 on a shape error */
+int    hdg_untangle(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                    float threshold, int32_t rule,
+                    int32_t* groups   /* [batch][nc] */,
+                    int32_t* tgroups  /* [batch][nc] or NULL */,
+                    uint64_t* ut      /* [batch][HDG_UT_SLOTS] */,
+                    void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
  *
  * Instead of an RCCL call between hdg_fwd_bwd and hdg_adam_tf, the step's reduction
