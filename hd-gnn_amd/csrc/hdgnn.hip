@@ -822,23 +822,6 @@ __device__ __forceinline__ f2 clamp_fma2_hi(const f2 x, const f2 a, const f2 b) 
 
 
 
-// inclusive scan over the 64 lanes of a wave with DPP only (GFX9 row_shr + row_bcast):
-// no LDS round trips.  Lanes shifted in from outside a row read 0 (bound_ctrl).
-template <int CTRL, int RMASK>
-__device__ __forceinline__ float dpp_in(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL,
-                                                               RMASK, 0xF, true));
-}
-__device__ __forceinline__ float wave_incl_scan_dpp(float v) {
-  v += dpp_in<0x111, 0xF>(v);   // row_shr:1
-  v += dpp_in<0x112, 0xF>(v);   // row_shr:2
-  v += dpp_in<0x114, 0xF>(v);   // row_shr:4
-  v += dpp_in<0x118, 0xF>(v);   // row_shr:8
-  v += dpp_in<0x142, 0xA>(v);   // row_bcast:15 -> rows 1, 3
-  v += dpp_in<0x143, 0xC>(v);   // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
 // ------------------------------------------------------------------------------
 // k_commit_step: the whole per-commit forward + backward, one 1024-thread block per
 // commit.  Node arrays live in LDS; one union region U is re-carved per phase
@@ -865,7 +848,7 @@ __host__ __device__ constexpr int nbuf_d(int smaxc) { return defer_cgrad(smaxc) 
 constexpr int NSL = NT_MID / HS;                // 51 node slices for (k, slice) matvecs
 
 struct StepLayout {   // offsets in 4-byte words into the dynamic LDS arena
-  int W, xs, xps, os, dxp, xsrt, perm, xu, cum, pxd, offr, offc, yb, nb, dnb, misc, u2, Mm, Xm,
+  int W, xs, xps, os, dxp, xu, cum, pxd, offr, offc, yb, nb, dnb, misc, u2, Mm, Xm,
       red, U, Uwords, total;
 };
 
@@ -881,8 +864,6 @@ __host__ __device__ inline StepLayout step_layout(int Ne, int Nc, int smaxc) {
   L.xps = o;  o += NE4;
   L.os = o;   o += NE4;
   L.dxp = o;  o += NE4;
-  L.xsrt = o; o += NE4;
-  L.perm = o; o += NE4;
   L.xu = o;   o += 2 * NE4;           // nd values, then +inf padding (E1's clamp-free search)
   L.cum = o;  o += NE4 + 4;
   L.pxd = o;  o += 2 * (NE4 + 4);     // f64 (offset is a multiple of 4 words)
@@ -899,8 +880,10 @@ __host__ __device__ inline StepLayout step_layout(int Ne, int Nc, int smaxc) {
   int u = 3 * NE4 * HS;                                            // P | E_bar | h
   const int uh = (nbuf_d(smaxc) + nbuf_h(smaxc)) * NC16 * HS + NG_MID * cred +   // hunk phases
                  (gam_lds(smaxc) ? NC16 * (NC16 + 8) : 0);
-  int ueb = 5 * NE4 * HS;                         // E3 bwd: P | E_bar | dq | dE | h/rho
-  const int ue2 = 2 * NE4 * HS + 2 * HS * (NE4 + 4) + (NT_MID / 64) * 4 * HS;   // E2 + rho
+  // E3 bwd: P | E_bar | dq | dE | h/rho, then E2's x-lists when they fit the hunk phases'
+  // words past these; E2's wave sums reuse the E_bar .. slots once every wave has left E2
+  int ueb = 5 * NE4 * HS;
+  const int ue2 = NE4 * HS + (NT_MID / 64) * 4 * HS;
   if (ue2 > ueb) ueb = ue2;
   if (uh > u) u = uh;
   if (ueb > u) u = ueb;
@@ -1064,7 +1047,7 @@ __device__ __forceinline__ void entity_fwd(const int t, const float* Ws,
                                            const int* offr, const int* offc,
                                            const float* xlr, const float* xlc,
                                            const int n0, const int n1, float* Ps,
-                                           float* __restrict__ EG, uint16_t* __restrict__ rq) {
+                                           float* __restrict__ EG, uint2* __restrict__ bq) {
 #pragma clang fp contract(off)
   // block-wide lane map (no cross-lane traffic left in E1): thread t takes node group
   // sub = t / 10 (102 nodes per pass), hidden units (2 kp, 2 kp + 1), kp = t % 10
@@ -1170,108 +1153,145 @@ __device__ __forceinline__ void entity_fwd(const int t, const float* Ws,
       const float2 P = make_float2(tot[0] + sp.x, tot[1] + sp.y);
       *reinterpret_cast<float2*>(Ps + i * HS + k0) = P;
       *reinterpret_cast<float2*>(EG + i * HS + k0) = P;
-      rq[i * HS + k0] = (uint16_t)br[0];
-      rq[i * HS + k0 + 1] = (uint16_t)br[1];
+      // the set boundaries of both sides for the backward (<= nd <= 256 each): one 8-byte
+      // store per (node, unit pair), rows in .x, columns in .y
+      bq[i * EG_L + kp] = make_uint2((uint32_t)br[0] | ((uint32_t)br[1] << 16),
+                                     (uint32_t)bc[0] | ((uint32_t)bc[1] << 16));
     }
   }
   if constexpr (HDG_SETPRIO) __builtin_amdgcn_s_setprio(0);
 }
 
-// E2 body: per-wave partial sums S0..S3 (dW1 rows, model_2.py:165-170 backward) for
-// the wave's nodes -> red2[wv][4][HS].  Same lane map and rounding contract as E1.
+// E2 body: the wave's partial sums S0..S3 (dW1 rows, model_2.py:165-170 backward) over its
+// nodes -> sv[4], folded over the wave's node groups (lanes 0..9 hold them).  Same lane map
+// and rounding contract as E1.  Node-local form: dz_ij = [z_ij > 0](rho_i + rho_j) summed
+// with the rho_j half re-ordered by columns, so node n contributes rho_n times
+//   S0: x_n |R_n| + sum_{i in C_n} x_i     S1: sum_{j in R_n} x_j + x_n |C_n|
+//   S2: |R_n| + |C_n|                      S3: sum_{j in R_n} a_nj + sum_{i in C_n} a_in
+// with R_n = {j != n : z_nj > 0} (row set) and C_n = {i != n : z_in > 0} (column set): counts
+// and x sums over a prefix or suffix of the sorted order (E1's boundaries, kept in bq) plus
+// the a = 1 corrections over the node's row and column x-lists.  No rho of another node is
+// read: a block needs its own half's rho only.
+template <bool WIDE>
 __device__ __forceinline__ void entity_bwd(const int lane, const int wv, const float* Ws,
                                            const float* xs, const int* cum, const double* pxd,
-                                           const int nd, const uint16_t* __restrict__ rq,
-                                           const float* rho, const float* Tr, const float* Tx,
-                                           const int TL, const int* xoff, const int* coff,
-                                           const uint8_t* idl, const float* xlr,
-                                           const int n0, const int n1, float* red2,
-                                           const int ne) {
+                                           const int nd, const uint2* __restrict__ bq,
+                                           const float* rho, const int* offr, const int* offc,
+                                           const float* xlr, const float* xlc,
+                                           const int n0, const int n1, f2 (&sv)[4]) {
 #pragma clang fp contract(off)
   const int sub = lane / EG_L, kp = lane - sub * EG_L, k0 = 2 * kp;
-  const EntUnit ea = ent_unit(Ws, k0 < HS ? k0 : 0), eb = ent_unit(Ws, k0 < HS ? k0 + 1 : 1);
+  const EntUnit ea = ent_unit(Ws, k0), eb = ent_unit(Ws, k0 + 1);
   const f2 w0 = {ea.w0, eb.w0}, w1 = {ea.w1, eb.w1}, c0 = {ea.c0, eb.c0}, dd = {ea.d, eb.d};
   const f2 ddS = dd * (f2){STEP_S, STEP_S};       // stepf2's c for [z0 + d > 0]
-  const bool ra[2] = {ea.w1 >= 0.f, eb.w1 >= 0.f};
+  const bool ra[2] = {ea.w1 >= 0.f, eb.w1 >= 0.f}, ca[2] = {ea.w0 >= 0.f, eb.w0 >= 0.f};
   f2 S0 = {0.f, 0.f}, S1 = S0, S2 = S0, S3 = S0;
   // rounds of 96 nodes; wave w takes nodes w + 16 s (s < 6) of a round, so the last,
-  // partial round's nodes land on as many waves -- and SIMDs -- as there are nodes
+  // partial round's nodes land on as many waves -- and SIMDs -- as there are nodes.  (Dealing
+  // whole trips to the waves that reach E2 first, those without an M13 tile, was measured
+  // and is slower: DESIGN.md 5.0.)
   constexpr int NWV = NT_MID / 64;
   int ms = 0;                                      // progress milestones (trip_prio)
   for (int base = n0; base + wv < n1; base += EG_N * NWV) {   // wave-uniform
     if constexpr (HDG_SETPRIO) trip_prio(ms++);
     const int i = base + wv + NWV * sub;
     const bool live = sub < EG_N && i < n1;
-    const int ic = live ? i : 0;
+    const int ic = live ? i : n0;                  // an own node: its rho and bq rows exist
     const float xi = xs[ic];
     const f2 u = __builtin_elementwise_fma((f2){xi, xi}, w0, c0);
-    const f2 vi = xi * w1;
-    const f2 ri = *reinterpret_cast<const f2*>(rho + ic * HS + (k0 < HS ? k0 : 0));
-    f2 s0, s1, s2, s3 = {0.f, 0.f};
+    const f2 v = xi * w1, x2 = {xi, xi};
+    f2 ri = *reinterpret_cast<const f2*>(rho + ic * HS + k0);
+    if (!live) ri = (f2){0.f, 0.f};
+    const uint2 qb = bq[ic * EG_L + kp];
+    // the a = 0 sets without the self pair: count and sum x of the row set R and of the
+    // column set C from the static tables, as E1 forms them
+    f2 b0, b1, b2;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int k = (k0 < HS ? k0 : 0) + h;
-      const int q = rq[ic * HS + k];
-      const int lo = ra[h] ? q : 0, hi = ra[h] ? nd : q;
-      const float cnt = (float)(cum[hi] - cum[lo]);
-      const float sx = (float)(pxd[hi] - pxd[lo]);
-      const int bm = cum[q];
-      const int ts = k * TL + 3 + (ra[h] ? ne - bm : bm);       // the set's scan-order count
-      float rs = fmaf(cnt, ri[h], Tr[ts]);                      // sum_{j in set} rho_i + rho_j
-      float a0 = xi * rs, a1 = fmaf(ri[h], sx, Tx[ts]);
-      if ((u[h] + vi[h]) > 0.f) {                                // remove j == i
-        const float r2 = 2.f * ri[h];
-        rs -= r2;
-        a0 -= xi * r2;
-        a1 -= xi * r2;
+      const int qr = (int)((qb.x >> (16 * h)) & 0xffffu), qc = (int)((qb.y >> (16 * h)) & 0xffffu);
+      const int rlo = ra[h] ? qr : 0, rhi = ra[h] ? nd : qr;
+      const int clo = ca[h] ? qc : 0, chi = ca[h] ? nd : qc;
+      float nr = (float)(cum[rhi] - cum[rlo]), nc = (float)(cum[chi] - cum[clo]);
+      float sxr = (float)(pxd[rhi] - pxd[rlo]), sxc = (float)(pxd[chi] - pxd[clo]);
+      if ((u[h] + v[h]) > 0.f) {             // the self pair lies in both sets: removed per side
+        nr -= 1.f;
+        nc -= 1.f;
+        sxr -= xi;
+        sxc -= xi;
       }
-      s0[h] = a0;
-      s1[h] = a1;
-      s2[h] = rs;
+      b0[h] = fmaf(xi, nr, sxc);
+      b1[h] = fmaf(xi, nc, sxr);
+      b2[h] = nr + nc;
     }
     if constexpr (HDG_SETPRIO) trip_prio(ms++);
-    f2 sd = {0.f, 0.f}, sx = sd;                     // sum dm, sum x_j dm
-    // row neighbours from the padded (id, x) lists: 4 ids in one u32 and 4 x values in one
-    // 16-byte read per step, identical across the node group's lanes (LDS broadcast)
-    // [z1 > 0] as stepf2(z0, d 2^64) (no z1 add); dm = ([z1 > 0] - [z0 > 0]) gs and s3 += [z1 > 0] gs
-    // as one fma: the same values as m1 gs - m0 gs and s3 + m1 gs (the steps are 0 or 1)
-    auto nbr = [&](const int j, const float xj) {
-      const f2 rj = *reinterpret_cast<const f2*>(rho + j * HS + k0);
+    // a = 1 corrections over the node's row x-list (z0 = u_n + x_j w1) and column x-list
+    // (z0 = fma(x_i, w0, c0) + v_n): m0 = [z0 > 0], m1 = [z0 + d > 0] as stepf2(z0, d 2^64),
+    // dm = m1 - m0.  Four x values per 16-byte read, identical across the node group's lanes
+    // (LDS broadcast); the NaN pads (the last 1-3 words of a list) are skipped: their steps
+    // are 0, but x dm would be NaN.  (Walking them with x made finite, one loop without the
+    // tail's branches, was measured and is slower: DESIGN.md 5.0.)
+    f2 sdr = {0.f, 0.f}, sxr = sdr, sdc = sdr, sxc = sdr, b3 = sdr;   // sum dm, sum x dm; sum m1
+    auto rowf = [&](const float xj) {
       const f2 z0 = u + xj * w1;
-      const f2 gs = ri + rj;                 // finite: step2(z) * gs == [z > 0] gs
-      const f2 st0 = step2(z0);
       const f2 st1 = HDG_STEPF ? stepf2(z0, ddS) : step2(z0 + dd);
-      const f2 dm = (st1 - st0) * gs;
-      sd += dm;
-      sx = __builtin_elementwise_fma((f2){xj, xj}, dm, sx);
-      s3 = __builtin_elementwise_fma(st1, gs, s3);
+      const f2 dm = st1 - step2(z0);
+      sdr += dm;
+      sxr = __builtin_elementwise_fma((f2){xj, xj}, dm, sxr);
+      b3 += st1;
     };
-    const int o0 = live ? xoff[ic] : 0;
-    const int d = live ? coff[ic + 1] - coff[ic] : 0;
-    int q = 0;
-    for (; q + 4 <= d; q += 4) {
-      const float4 xv = *reinterpret_cast<const float4*>(xlr + o0 + q);
-      const uint32_t jw = *reinterpret_cast<const uint32_t*>(idl + o0 + q);
-      nbr(jw & 0xffu, xv.x);
-      nbr((jw >> 8) & 0xffu, xv.y);
-      nbr((jw >> 16) & 0xffu, xv.z);
-      nbr(jw >> 24, xv.w);
-    }
-    if (q < d) {                             // 1-3 left (group-uniform); pads are skipped
-      const float4 xv = *reinterpret_cast<const float4*>(xlr + o0 + q);
-      const uint32_t jw = *reinterpret_cast<const uint32_t*>(idl + o0 + q);
-      nbr(jw & 0xffu, xv.x);
-      if (q + 1 < d) nbr((jw >> 8) & 0xffu, xv.y);
-      if (q + 2 < d) nbr((jw >> 16) & 0xffu, xv.z);
-    }
-    s0 = __builtin_elementwise_fma((f2){xi, xi}, sd, s0);
-    s1 += sx;
-    s2 += sd;
-    if (live) { S0 += s0; S1 += s1; S2 += s2; S3 += s3; }
+    auto colf = [&](const float xj) {
+      const f2 z0 = __builtin_elementwise_fma((f2){xj, xj}, w0, c0) + v;
+      const f2 st1 = HDG_STEPF ? stepf2(z0, ddS) : step2(z0 + dd);
+      const f2 dm = st1 - step2(z0);
+      sdc += dm;
+      sxc = __builtin_elementwise_fma((f2){xj, xj}, dm, sxc);
+      b3 += st1;
+    };
+    auto walk = [&](const float* xl, int o, const int o1, auto f) {
+      // WIDE (the lists did not fit LDS and are read from HBM: long lists, dense a): sixteen
+      // values per trip, the four 16-byte reads in flight together.  Not in the LDS copy:
+      // the extra loop cost the glide block 0.3 us.
+      for (; WIDE && o + 16 < o1; o += 16) {
+        float4 xv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xv[c] = *reinterpret_cast<const float4*>(xl + o + 4 * c);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          f(xv[c].x);
+          f(xv[c].y);
+          f(xv[c].z);
+          f(xv[c].w);
+        }
+      }
+      for (; o + 4 < o1; o += 4) {
+        const float4 xv = *reinterpret_cast<const float4*>(xl + o);
+        f(xv.x);
+        f(xv.y);
+        f(xv.z);
+        f(xv.w);
+      }
+      if (o < o1) {                          // the list's last four: 1-4 values, then pads
+        const float4 xv = *reinterpret_cast<const float4*>(xl + o);
+        f(xv.x);
+        if (xv.y == xv.y) f(xv.y);
+        if (xv.z == xv.z) f(xv.z);
+        if (xv.w == xv.w) f(xv.w);
+      }
+    };
+    walk(xlr, live ? offr[ic] : 0, live ? offr[ic + 1] : 0, rowf);
+    if constexpr (HDG_SETPRIO) trip_prio(ms++);
+    walk(xlc, live ? offc[ic] : 0, live ? offc[ic + 1] : 0, colf);
+    b0 += __builtin_elementwise_fma(x2, sdr, sxc);
+    b1 += __builtin_elementwise_fma(x2, sdc, sxr);
+    b2 += sdr + sdc;
+    S0 = __builtin_elementwise_fma(ri, b0, S0);
+    S1 = __builtin_elementwise_fma(ri, b1, S1);
+    S2 = __builtin_elementwise_fma(ri, b2, S2);
+    S3 = __builtin_elementwise_fma(ri, b3, S3);
   }
   if constexpr (HDG_SETPRIO) __builtin_amdgcn_s_setprio(0);
-  // fold the 6 node groups (lanes kp + 10 s), then lanes 0..9 write the wave's sums
-  f2 sv[4] = {S0, S1, S2, S3};
+  // fold the 6 node groups (lanes kp + 10 s): lanes 0..9 then hold the wave's sums
+  sv[0] = S0; sv[1] = S1; sv[2] = S2; sv[3] = S3;
 #pragma unroll
   for (int w = 0; w < 4; ++w)
 #pragma unroll
@@ -1281,13 +1301,6 @@ __device__ __forceinline__ void entity_bwd(const int lane, const int wv, const f
       a += __shfl_down(a, EG_L) + __shfl_down(a, 2 * EG_L);
       sv[w][h] = a;
     }
-  if (lane < EG_L) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      red2[(wv * 4 + w) * HS + k0] = sv[w].x;
-      red2[(wv * 4 + w) * HS + k0 + 1] = sv[w].y;
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------
@@ -1306,7 +1319,7 @@ __device__ __forceinline__ void entity_bwd(const int lane, const int wv, const f
 // status word, NaN CE / probs / logits, fault slot that makes the Adam kernels skip the
 // update), never a hang.  v must not change between send and receive; n is even.
 // ------------------------------------------------------------------------------
-// tag of exchange slot s (1..5) in the pair's launch epoch e (a per-commit counter the
+// tag of exchange slot s (1..4) in the pair's launch epoch e (a per-commit counter the
 // pair reads at its start and block 0 advances after the last exchange): stale words
 // of earlier launches carry other tags, so the inboxes are never cleared; the xor keeps
 // a tag different from the word's own fill pattern in a garbage workspace
@@ -1314,7 +1327,6 @@ __device__ __forceinline__ uint32_t xtag(const uint32_t epoch, const int slot) {
   return (epoch * 8u + (uint32_t)slot) ^ 0xC0DE5A5Au;
 }
 constexpr int XSLOTS = 4;                       // H, D_tau, dn partials; n partial + o rows
-constexpr int XRHO = 256 * HS / 2;              // + the rho rows of a node half (Ne <= 256)
 constexpr unsigned long long XWAIT = 2000000ull;   // s_memrealtime ticks (100 MHz) = 20 ms
 typedef uint32_t xu4 __attribute__((ext_vector_type(4)));
 
@@ -1339,7 +1351,6 @@ __device__ __forceinline__ void pair_send(const float* v, const int n, xu4* __re
     xstore(out + e, (xu4){__float_as_uint(v[2 * e]), tag, __float_as_uint(v[2 * e + 1]), tag});
 }
 
-template <bool ADD = true>
 __device__ __forceinline__ bool pair_recv_add(float* v, const int n, xu4* __restrict__ in,
                                               const uint32_t tag, const int t) {
   bool late = false;
@@ -1350,13 +1361,8 @@ __device__ __forceinline__ bool pair_recv_add(float* v, const int n, xu4* __rest
       if (__builtin_amdgcn_s_memrealtime() - t0 > XWAIT) { late = true; break; }
       w = xload(in + e);
     }
-    if (ADD) {
-      v[2 * e] += __uint_as_float(w.x);
-      v[2 * e + 1] += __uint_as_float(w.z);
-    } else {                                 // the partner's own rows: taken as they are
-      v[2 * e] = __uint_as_float(w.x);
-      v[2 * e + 1] = __uint_as_float(w.z);
-    }
+    v[2 * e] += __uint_as_float(w.x);
+    v[2 * e + 1] += __uint_as_float(w.z);
   }
   __syncthreads();
   return late;
@@ -1427,7 +1433,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   const int prow = SPLIT ? 2 * b + h : b;            // this block's partial-gradient row
   bool xlate = false;
   constexpr int XS = 16 * SMAXC * HS / 2;            // 16-byte words per inbox slot
-  constexpr int XB = XSLOTS * XS + XRHO;             // per block inbox
+  constexpr int XB = XSLOTS * XS;                    // per block inbox
   xu4* xin = SPLIT ? reinterpret_cast<xu4*>(xch) + (size_t)(2 * b + h) * XB : nullptr;
   xu4* xout = SPLIT ? reinterpret_cast<xu4*>(xch) + (size_t)(2 * b + 1 - h) * XB : nullptr;
   // per-commit launch epoch of the pair's exchange tags (after the 2B inboxes)
@@ -1488,8 +1494,6 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   float* xps = lds + L.xps;
   float* os = lds + L.os;
   float* dxp = lds + L.dxp;
-  float* xsrt = lds + L.xsrt;
-  int* perm = (int*)(lds + L.perm);
   float* xu = lds + L.xu;
   int* cum = (int*)(lds + L.cum);
   double* pxd = (double*)(lds + L.pxd);
@@ -1527,7 +1531,8 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   constexpr int GLD = GAML ? NC16 + 8 : NC16;
   constexpr bool DEFER = TRAIN && defer_cgrad(SMAXC);   // M9 form (defer_cgrad above)
   float* gamG = gamg + (size_t)b * NC16 * NC16;
-  uint16_t* rq = rowq + (size_t)b * Ne * HS;
+  // E1's set boundaries [Ne][HS / 2] (rows | columns of a unit pair), read back by E2
+  uint2* bq = reinterpret_cast<uint2*>(rowq) + (size_t)b * Ne * EG_L;
   const float Nc1 = (float)(Nc - 1);
   const float twoNe1 = 2.f * (float)(Ne - 1);
 
@@ -1551,21 +1556,17 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const int q = t + u * NT_MID;
     wr_[u] = q < NP ? Wg[q + (q >= H1_W1 ? ee_ins : 0)] : 0.f;
   }
-  float xv = 0.f, xsv = 0.f, xuv = 0.f;
-  int pmv = 0, cmv = 0, orv = 0, ocv = 0;
+  float xv = 0.f, xuv = 0.f;
+  int cmv = 0, orv = 0, ocv = 0;
   double pxv = 0.0;
   uint32_t ybv = 0u;
-  if (t < Ne) {
-    xv = x[(size_t)b * Ne + t];
-    xsv = reinterpret_cast<const float*>(pp + PL.xsrt)[t];
-    pmv = reinterpret_cast<const int*>(pp + PL.perm)[t];
-  }
+  if (t < Ne) xv = x[(size_t)b * Ne + t];
   if (t <= Ne) {   // nd <= Ne: loaded without waiting for nd (stored below for t <= nd)
     if (t < Ne) xuv = reinterpret_cast<const float*>(pp + PL.xu)[t];
     cmv = reinterpret_cast<const int*>(pp + PL.cum)[t];
     pxv = reinterpret_cast<const double*>(pp + PL.pxd)[t];
   }
-  if (t <= Ne) {   // x-list offsets (E1); the id offsets for E2 are restaged before E2
+  if (t <= Ne) {   // x-list offsets (E1 and E2)
     orv = reinterpret_cast<const int*>(pp + PL.xoffr)[t];
     ocv = reinterpret_cast<const int*>(pp + PL.xoffc)[t];
   }
@@ -1590,11 +1591,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     l2 = wave_sum(l2);
     if (lane == 0) red[wv * 32] = l2;
   }
-  if (t < Ne) {
-    xs[t] = xv;
-    xsrt[t] = xsv;
-    perm[t] = pmv;
-  }
+  if (t < Ne) xs[t] = xv;
   if (t <= nd) {
     cum[t] = cmv;
     pxd[t] = pxv;
@@ -1648,9 +1645,9 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   const int nlo = SPLIT && h ? (Ne + 1) / 2 : 0, nhi = SPLIT && !h ? (Ne + 1) / 2 : Ne;
   if (lfit)        // two inlined copies: the staged lists are read as LDS, not flat
     entity_fwd(t, Ws, xs, xu, cum, pxd, nd, offr, offc, U + NE4 * HS, U + NE4 * HS, nlo, nhi, Ps,
-               EG, rq);
+               EG, bq);
   else
-    entity_fwd(t, Ws, xs, xu, cum, pxd, nd, offr, offc, xlistg, xlistg, nlo, nhi, Ps, EG, rq);
+    entity_fwd(t, Ws, xs, xu, cum, pxd, nd, offr, offc, xlistg, xlistg, nlo, nhi, Ps, EG, bq);
   WAVE_STAMP(0);
   __syncthreads();
   MID_STAMP();
@@ -2389,6 +2386,9 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     if constexpr (STAMPS) MID_STAMP();
     xlate |= pair_recv_add(dnb, 2 * Nc, xin + 2 * XS, xtag(epoch, 3), t);
     if (dnout) xlate |= pair_recv_add(dnc, 2 * Nc, xin + 2 * XS + Nc, xtag(epoch, 3), t);
+    // the pair's last exchange: next epoch.  Block 0 has received from its partner, which
+    // read the epoch at its start, long before it sent.
+    if (h == 0 && t == 0) *xctr = epoch + 1u;
   } else {
     __syncthreads();
   }
@@ -2405,6 +2405,19 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   // ---- M11: cross-graph backward: dx'_I = sum_c dn_c[0] ks[c][I] + dn_c[1] kt[c][I] ----
   //   4 hunk ranges (one per group) -> partial rows in the dq slot of U
   float* dxpart = U + 3 * NE4 * HS;
+  // E2's neighbour x-lists (rows | columns, as staged for E1): back into LDS past the five
+  // node slots of the E3 backward when they fit the words the hunk phases leave there (dead
+  // since the barrier above), else E2 reads them from the prepared buffer.  The first LQ
+  // float4 per thread are fetched here and stored after M11's loop, which hides the round trip.
+  float* xl2 = U + 5 * NE4 * HS;
+  const bool lfit2 = xwords <= L.Uwords - 5 * NE4 * HS;
+  float4 lv2[LQ];
+#pragma unroll
+  for (int u = 0; u < LQ; ++u) {
+    const int w = 4 * (t + u * NT_MID);
+    lv2[u] = (lfit2 && w < xwords) ? *reinterpret_cast<const float4*>(pp + PL.xl + w)
+                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   {
     const uint16_t* ks = reinterpret_cast<const uint16_t*>(pp + PL.ks);
     const uint16_t* kt = reinterpret_cast<const uint16_t*>(pp + PL.kt);
@@ -2422,16 +2435,22 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
       dxpart[gx * NE4 + I] = a0 + a1;
     }
   }
+  if (lfit2) {
+#pragma unroll
+    for (int u = 0; u < LQ; ++u) {
+      const int w = 4 * (t + u * NT_MID);
+      if (w < xwords) *reinterpret_cast<float4*>(xl2 + w) = lv2[u];
+    }
+    for (int w = 4 * (t + LQ * NT_MID); w < xwords; w += 4 * NT_MID)   // the rest of long lists
+      *reinterpret_cast<float4*>(xl2 + w) = *reinterpret_cast<const float4*>(pp + PL.xl + w);
+  }
   __syncthreads();
   MID_STAMP();
 
   // ---- M12: mlp2_entity_B1 backward.  U re-carved: P | E_bar | dq | dE | ... | h (-> rho)
   float* dq = U + 2 * NE4 * HS;
   float* dE = U + 3 * NE4 * HS;
-  const int rho_off = (4 * NE4 * HS > NE4 * HS + 2 * HS * (NE4 + 4) + (NT_MID / 64) * 4 * HS)
-                          ? 4 * NE4 * HS
-                          : NE4 * HS + 2 * HS * (NE4 + 4) + (NT_MID / 64) * 4 * HS;
-  float* hB = U + rho_off;                          // h, overwritten by rho row block by row block
+  float* hB = U + 4 * NE4 * HS;                     // h, overwritten by rho row block by row block
   float* rho = hB;
   float* dw2p = Xm;                                 // [row block][21] partial dw2', db2'
   for (int i = nlo + t; i < nhi; i += NT_MID) {
@@ -2456,20 +2475,6 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   }
   __syncthreads();
   MID_STAMP();
-  // E2's row neighbour lists and row CSR offsets: fetched here into registers (one HBM
-  // round trip hidden behind M12 / M13 and the rho exchange), written to LDS after the
-  // exchange (the P slot they go to is read by dW5)
-  const int rl = (int)pp[PL.xoffc];                 // padded row-list length (multiple of 4)
-  const bool rfit = rl / 4 + rl <= NE4 * HS;
-  const int xl2o = (rl / 4 + 3) & ~3;              // staged x values after the ids
-  uint32_t e2id = 0u;
-  float4 e2x = make_float4(0.f, 0.f, 0.f, 0.f);
-  int e2off = 0;
-  if (rfit) {
-    if (t < rl / 4) e2id = pp[PL.lists + t];
-    if (4 * t < rl) e2x = *reinterpret_cast<const float4*>(pp + PL.xl + 4 * t);
-  }
-  if (t <= Ne) e2off = reinterpret_cast<const int*>(pp + PL.offr)[t];
   // row-local chain per 16-row block: dq = [h > 0] w2' do;  dE = dq W1'[1:]^T;
   // rho = dE W5^T (into h's rows, consumed first); partial dw2' / db2' of the block
   for (int rb = (nlo >> 4) + wv; rb <= ((nhi - 1) >> 4); rb += NT_MID / 64) {   // wave-uniform
@@ -2566,15 +2571,16 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     }
   }
   __syncthreads();
-  // trailer zeros (fault slot: t = 2) before the rho send, whose vmcnt(0) completes them:
-  // a late thread's fault store at the end then lands after them
+  // trailer zeros (fault slot: t = 2): completed by the vmcnt(0) in front of the barrier that
+  // follows E2, so a late thread's fault store at the end lands after them
   if (t < HDG_TRAILER - 2) pb[NP + 2 + t] = 0.f;
   if (t == 2) fsl[prow] = 0.f;                      // same thread as the fault slot
-  if constexpr (SPLIT) pair_send(rho + nlo * HS, (nhi - nlo) * HS, xout + XSLOTS * XS, xtag(epoch, 5) ^ xsend, t);
   MID_STAMP();
   // ---- M13: reductions over rows: dW1' = [x, E_bar, 1]^T dq (waves 0-3),
   //      dW5 = [P, 1]^T dE (waves 4-7; row 20 -> db5 / 2(Ne-1)), dw2' / db2' (wave 8);
-  //      split mode: over the own node half (partial gradients), the rho exchange overlaps
+  //      split mode: over the own node half (partial gradients).  No barrier follows: E2 reads
+  //      nothing M13 writes and writes no LDS, so a wave runs from its tile straight into E2
+  //      (waves 9-15 at once).
   if (wv < 4) {
     const int row0 = (wv >> 1) * 16, col0 = (wv & 1) * 16;
     const int lr = row0 + (lane & 15), kc = col0 + (lane & 15);
@@ -2612,111 +2618,37 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     pb[lane < HS ? E3_W2 + lane : E3_B2] = acc;
   }
   if (t < 4) pb[TH1 + t] = 0.f;                     // map_theta*: data-independent
-  if constexpr (SPLIT) {                             // the partner half's rho rows
-    const int plo = h ? 0 : (Ne + 1) / 2, phi = h ? (Ne + 1) / 2 : Ne;
-    xlate |= pair_recv_add<false>(rho + plo * HS, (phi - plo) * HS, xin + XSLOTS * XS,
-                                  xtag(epoch, 5), t);
-    if (h == 0 && t == 0) *xctr = epoch + 1u;     // last exchange of the pair: next epoch
-  } else {
-    __syncthreads();
-  }
-  MID_STAMP();
+  MID_STAMP();                                       // (thread 0: the end of wave 0's tile)
 
   // ---- E2: mlp_entity_B1 first-layer backward -----------------------------------------
   //   dz_ij = [z_ij > 0] (rho_i + rho_j)  (P_i holds row i AND column i of the grid)
   //   S0 = sum x_i dz, S1 = sum x_j dz, S2 = sum dz, S3 = sum a dz  ->
   //   dW1[0] = S0, dW1[1] = S1, dW1[2] = S2 - S3, dW1[3] = S3, db1 = S2.
-  //   The a = 0 part reuses the forward's row sets: per k, sums of rho and of x*rho over
-  //   every suffix (w1 >= 0) or prefix (w1 < 0) of the x-sorted order, one wave per scan,
-  //   so each set sum is one table read.  a = 1 corrections over the set bits of row i,
-  //   same (node, k) lane map as E1.
-  const int TL = NE4 + 4;
-  float* Tr = U + NE4 * HS;                // [HS][TL]   (E_bar, dq, dE slots are dead)
-  float* Tx = Tr + HS * TL;                // [HS][TL]
-  float* red2 = Tx + HS * TL;              // [16 waves][4][HS]  (ends below rho_off)
-  // row neighbour (id, x) lists (padded, offsets xoffr still in offr), staged into the P
-  // slot (dead after dW5) when they fit (rl <= 4096 < 4 NT_MID: one id word and one x
-  // float4 per thread, fetched before M12); offc <- the compact row CSR (degrees)
-  if (rfit) {
-    if (t < rl / 4) Ps[t] = __builtin_bit_cast(float, e2id);
-    if (4 * t < rl) *reinterpret_cast<float4*>(Ps + xl2o + 4 * t) = e2x;
-  }
-  if (t <= Ne) offc[t] = e2off;
+  //   Node-local (entity_bwd): each own node's rho times rho-free counts and x sums of its
+  //   row and column sets -- the forward's set boundaries and the static prefix tables, plus
+  //   the a = 1 corrections over its two x-lists; same (node, k) lane map as E1.  Nothing of
+  //   the partner half is needed: split mode has no rho exchange, and nothing is scanned.
   WAVE_STAMP(3);
-  // The scan inputs in scan order, unit-major: Tr[k][4 + s] = rho of the node at scan slot
-  // s (sorted slot m = s for the prefix units, w1 < 0; Ne - 1 - s for the suffix units), Tx
-  // likewise x rho -- one block-wide pass over rho's rows (a node's 20 units on 20 lanes),
-  // instead of each unit's wave gathering its column through perm: a column of the 20-word
-  // row pitch lies on 8 of the 32 banks, a 4-way conflict on every gathered read.
-  for (int e = t; e < Ne * HS; e += NT_MID) {
-    const int m = e / HS, k = e - m * HS;
-    const float v = rho[perm[m] * HS + k];
-    const int sl = Ws[E1_W1 + HS + k] >= 0.f ? Ne - 1 - m : m;
-    Tr[k * TL + 4 + sl] = v;
-    Tx[k * TL + 4 + sl] = v * xsrt[m];
-  }
-  __syncthreads();
-  // Per-unit inclusive scans in place: T[k][3 + c] = the sum over the first c scan slots
-  // (T[k][3] = 0), so a suffix unit's set [m, Ne) is c = Ne - m and a prefix unit's [0, m)
-  // is c = m (entity_bwd).  A lane owns 4 consecutive slots: one 16-byte read and write.
-  // TB: 1 = the rho table, 2 = the x rho table, 3 = both
-  auto unit_scan = [&](const int k, auto tbc) {
-    constexpr int TB = decltype(tbc)::value;
-    float* T0 = Tr + k * TL;
-    float* T1 = Tx + k * TL;
-    const int s0 = 4 * lane;                      // NE4 <= 256: one float4 per lane
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    if (s0 < Ne) {
-      if constexpr (TB & 1) a0 = *reinterpret_cast<const float4*>(T0 + 4 + s0);
-      if constexpr (TB & 2) a1 = *reinterpret_cast<const float4*>(T1 + 4 + s0);
-    }
-    const float v0[4] = {a0.x, a0.y, a0.z, a0.w}, v1[4] = {a1.x, a1.y, a1.z, a1.w};
-    float run0[4], run1[4];
-    float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const bool in = s0 + q < Ne;                  // slots past Ne hold no node
-      r0 += in ? v0[q] : 0.f;
-      r1 += in ? v1[q] : 0.f;
-      run0[q] = r0;
-      run1[q] = r1;
-    }
-    const float off0 = (TB & 1) ? wave_incl_scan_dpp(r0) - r0 : 0.f;
-    const float off1 = (TB & 2) ? wave_incl_scan_dpp(r1) - r1 : 0.f;
-    if (s0 < Ne) {
-      if constexpr (TB & 1)
-        *reinterpret_cast<float4*>(T0 + 4 + s0) =
-            make_float4(off0 + run0[0], off0 + run0[1], off0 + run0[2], off0 + run0[3]);
-      if constexpr (TB & 2)
-        *reinterpret_cast<float4*>(T1 + 4 + s0) =
-            make_float4(off1 + run1[0], off1 + run1[1], off1 + run1[2], off1 + run1[3]);
-    }
-    if (lane == 0) {
-      if constexpr (TB & 1) T0[3] = 0.f;
-      if constexpr (TB & 2) T1[3] = 0.f;
-    }
-  };
-  // units 0..15: both tables on wave k; units 16.. (HS > 16): one table each on waves
-  // 4, 5, ...: the second unit no longer runs alone on waves 0-3 at the phase's tail
-  constexpr int NWV = NT_MID / 64;
-  static_assert(HS <= NWV + (NWV - 4) / 2, "scan map: extra units beyond waves 4..15");
-  if (wv < HS) unit_scan(wv, std::integral_constant<int, 3>{});
-  if (wv >= 4 && wv < 4 + 2 * (HS - NWV)) {
-    const int k = NWV + ((wv - 4) >> 1);
-    if ((wv - 4) & 1) unit_scan(k, std::integral_constant<int, 2>{});
-    else unit_scan(k, std::integral_constant<int, 1>{});
-  }
-  WAVE_STAMP(4);
-  __syncthreads();
-  MID_STAMP();
-  if (rfit)
-    entity_bwd(lane, wv, Ws, xs, cum, pxd, nd, rq, rho, Tr, Tx, TL, offr, offc,
-               reinterpret_cast<const uint8_t*>(Ps), Ps + xl2o, nlo, nhi, red2, Ne);
+  f2 e2s[4];
+  if (lfit2)       // two inlined copies: the staged lists are read as LDS, not flat
+    entity_bwd<false>(lane, wv, Ws, xs, cum, pxd, nd, bq, rho, offr, offc, xl2, xl2, nlo, nhi, e2s);
   else
-    entity_bwd(lane, wv, Ws, xs, cum, pxd, nd, rq, rho, Tr, Tx, TL, offr, offc,
-               reinterpret_cast<const uint8_t*>(pp + PL.lists),
-               reinterpret_cast<const float*>(pp + PL.xl), nlo, nhi, red2, Ne);
+    entity_bwd<true>(lane, wv, Ws, xs, cum, pxd, nd, bq, rho, offr, offc, xlistg, xlistg, nlo, nhi,
+                     e2s);
   WAVE_STAMP(2);
+  // every wave is past M13 and E2 here: the E_bar .. slots are dead and take the waves' sums.
+  // The vmcnt(0) completes this thread's trailer zeros (and M13's stores) before the
+  // barrier, hence before any thread's fault stores below.
+  float* red2 = U + NE4 * HS;              // [16 waves][4][HS]
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (lane < EG_L) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      red2[(wv * 4 + w) * HS + 2 * lane] = e2s[w].x;
+      red2[(wv * 4 + w) * HS + 2 * lane + 1] = e2s[w].y;
+    }
+  }
   __syncthreads();
   if (t < 4 * HS) {
     const int w = t / HS, k = t - w * HS;
@@ -2922,14 +2854,14 @@ Work work_layout(const hdg_shape* s) {
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 63) & ~(size_t)63; return r; };
   w.Esave = take(3 * B * Ne * HS);
-  w.rowq = take((B * Ne * HS + 1) / 2);     // u16
+  w.rowq = take(B * Ne * HS);               // u16 row and column set boundaries (E1 -> E2)
   w.gam = take(B * NC16 * NC16);
   // one partial row per block (2 per commit split), then the rows' fault slots (2B floats)
   w.part = take(2 * B * (size_t)NPART + 2 * B);
   w.aux = take(8);
   // block-pair inboxes (split mode): [B][2 halves][XSLOTS][NC16*HS] u64 (value, tag) words;
   // zero at allocation, left zero by every completed launch
-  w.xch = take(2 * B * 4 * ((size_t)XSLOTS * NC16 * HS / 2 + XRHO) + B);   // + epochs
+  w.xch = take(2 * B * 4 * ((size_t)XSLOTS * NC16 * HS / 2) + B);   // + epochs
   w.total = o;
   return w;
 }

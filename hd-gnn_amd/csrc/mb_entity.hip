@@ -7,7 +7,7 @@ namespace {
 
 template <int ABL>
 __global__ __launch_bounds__(1024) void mb_e1(int Ne, int iters, float* out, float* EG,
-                                              uint16_t* rq) {
+                                              uint2* bq) {
   __shared__ float Ws[2128];
   __shared__ float xs[256], xu[256], Ps[256 * HS];
   __shared__ int cum[260], offr[260], offc[260];
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(1024) void mb_e1(int Ne, int iters, float* out, flo
   __syncthreads();
   for (int it = 0; it < iters; ++it) {
     entity_fwd<ABL>(t, Ws, xs, xu, cum, pxd, 10, offr, offc, lr, lc, 0, Ne, Ps,
-                    EG + (size_t)b * Ne * HS, rq + (size_t)b * Ne * HS);
+                    EG + (size_t)b * Ne * HS, bq + (size_t)b * Ne * EG_L);
     __syncthreads();
   }
   if (t == 0) out[b] = Ps[7] + Ps[300];
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(1024) void mb_e1(int Ne, int iters, float* out, flo
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
 template <int ABL>
-float run(float* out, float* EG, uint16_t* rq, int blocks, int iters) {
+float run(float* out, float* EG, uint2* rq, int blocks, int iters) {
   hipEvent_t a, b;
   hipEventCreate(&a);
   hipEventCreate(&b);
@@ -62,10 +62,10 @@ float run(float* out, float* EG, uint16_t* rq, int blocks, int iters) {
 
 int main() {
   float *out, *EG;
-  uint16_t* rq;
+  uint2* rq;
   CK(hipMalloc(&out, 4096 * sizeof(float)));
   CK(hipMalloc(&EG, 100 * 256 * HS * sizeof(float)));
-  CK(hipMalloc(&rq, 100 * 256 * HS * sizeof(uint16_t)));
+  CK(hipMalloc(&rq, 100 * 256 * EG_L * sizeof(uint2)));
   const int B = 100, IT = 20;
   printf("entity_fwd Ne=200 (us per call, %d blocks x 1024 thr)\n", B);
   printf("  full              %8.2f\n", run<0>(out, EG, rq, B, IT));

@@ -30,7 +30,9 @@ for _ in range(3):
                                             ctypes.c_void_p(st.data_ptr()), eng._stream()))
 torch.cuda.synchronize()
 allst = st.cpu().numpy().astype(np.int64)
-nblk = 2 * B if allst[B * 32] > 0 or allst[(2 * B - 1) * 32] > 0 else B
+# split mode: row B is a phase row (its slots 6, 7 are stamped); one block per commit: the
+# wave rows [B][16][8] start there, and no wave slot above 5 is ever written
+nblk = 2 * B if allst[B * 32 + 6] > 0 and allst[B * 32 + 7] > 0 else B
 s = allst[:2 * B * 32].reshape(2 * B, 32)
 wst = allst[nblk * 32: nblk * 32 + nblk * 128].reshape(nblk, 16, 8)
 s = s[:nblk]
@@ -46,8 +48,8 @@ print("block start skew: median %.2f us, max %.2f us; first start -> last end %.
 
 # per-wave stamps: (slot, phase stamp it is measured from, label)
 WAVE = [(5, 0, "stage staged (from kernel start)"), (0, 1, "E1 done (from E1 start)"), (1, 8, "M7 loop done (from M7 start)"),
-        (3, 19, "scan start (from M13 start)"), (4, 19, "scans done (from M13 start)"),
-        (2, 21, "E2 done (from E2 start)")]
+        # the M13 stamp is the third from the end in both block forms (19 of 22 in split mode)
+        (3, n - 3, "E2 start (from M13 start)"), (2, n - 3, "E2 done (from M13 start)")]
 for slot, ph, label in WAVE:
     if wst[:, :, slot].max() == 0:
         continue
