@@ -38,7 +38,7 @@ constexpr size_t OFF_AUX = OFF_EPOCH + 256 * 4;     // f32 [8] loss terms + Adam
 constexpr size_t OFF_GLOC = OFF_AUX + 8 * 4;        // f32 [GLENP] the rank's own gradient
 constexpr size_t BYTES = OFF_GLOC + GLENP * 4;      //   (general path, hdg_train_step_dp)
 constexpr unsigned long long WAIT_DEFAULT = 1000000000ull;   // 10 s of s_memrealtime
-static_assert(GLENP % RED_P == 0 && NBLK <= 256, "mailbox layout");
+static_assert(GLENP % RED_P == 0 && NBLK <= 256 && AUX_LEN <= 8, "mailbox layout");
 static_assert(GLENP >= 3129 + HDG_TRAILER, "every variant's gradient fits a mailbox row");
 enum { SUM = 0, PART = 1, GRAD = 2 };
 }  // namespace dpk
@@ -65,6 +65,56 @@ __device__ __forceinline__ xu2 dload2(const uint32_t* p) {
 }
 __device__ __forceinline__ uint32_t* dp_slot(uint32_t* box, uint32_t par, int src, int p) {
   return box + 2 * (((size_t)par * dpk::MAXW + src) * dpk::GLENP + p);
+}
+
+// A peer's word of epoch e from the own mailbox: polled until its tag arrives or `wait`
+// ticks have passed (late; the value is then whatever the slot held).  bad = the peer's
+// fault bit.
+__device__ __forceinline__ float dp_recv(const uint32_t* in, const uint32_t e,
+                                         const unsigned long long wait, bool& late, bool& bad) {
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  xu2 wd = dload2(in);
+  while ((wd.y >> 1) != (e & 0x7FFFFFFFu)) {
+    if (__builtin_amdgcn_s_memrealtime() - t0 > wait) { late = true; break; }
+    __builtin_amdgcn_s_sleep(1);
+    wd = dload2(in);
+  }
+  bad = (wd.y & 1u) != 0u;
+  return __uint_as_float(wd.x);
+}
+
+// What the owner of slot p (thread l of its group) does once the world's words are in
+// vals: the rank-order sum -> gout (a NaN CE and the status word when a peer was late) and,
+// with ADAM, the count / fault slots and the loss stats into stats, TF1 ApplyAdam of a
+// parameter slot (adam_tf.h; skipped after a late or faulted peer) and, on the step's first
+// slot, the new beta powers.
+template <bool ADAM>
+__device__ __forceinline__ void dp_own_slot(
+    const float (*vals)[RED_P], const int world, const int l, const int p, const int np,
+    const bool first, const bool anylate, const bool anybad, bool upd, const float w,
+    const float m0, const float v0, float* __restrict__ gout, float* __restrict__ params,
+    float* __restrict__ mm, float* __restrict__ vv, float* __restrict__ bpow,
+    const float* __restrict__ aux, const float lr, const float inv_pairs,
+    float* __restrict__ stats, uint32_t* __restrict__ status) {
+  float tot = 0.f;
+  for (int q = 0; q < world; ++q) tot += vals[q][l];
+  if (ADAM && p == np + HDG_TR_CE && anylate) tot = __builtin_nanf("");
+  gout[p] = tot;
+  if (anylate && threadIdx.x == 0 && status) xstore1(status, HDG_STATUS_DP_TIMEOUT);
+  if constexpr (ADAM) {
+    if (stats && p >= np + HDG_TR_COUNT && p <= np + HDG_TR_FAULT)   // count parts, fault
+      stats[4 + (p - np - HDG_TR_COUNT)] = tot;
+    if (p == np + HDG_TR_CE && stats)
+      step_stats_store(stats, tot, inv_pairs, aux[AUX_LMAP], aux[AUX_LPARA]);
+    if (anylate || anybad) upd = false;
+    if (upd)
+      adam_tf_slot(p, np, tot, w, m0, v0, lr * aux[AUX_LRF], aux[AUX_N1], aux[AUX_N2], params, mm,
+                   vv);
+    if (first && upd) {
+      bpow[0] = aux[AUX_B1P];
+      bpow[1] = aux[AUX_B2P];
+    }
+  }
 }
 
 // MODE SUM:  gout = world sum of src[0..glen)                       (hdg_dp_allreduce)
@@ -123,58 +173,16 @@ __global__ __launch_bounds__(1024) void k_dp_tail(const float* __restrict__ src,
   bool late = false, rbad = false;
   if (mine) {
     float v = gl[l];
-    if (r != d.rank) {
-      const uint32_t* in = dp_slot(own, par, r, p);
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      xu2 wd = dload2(in);
-      while ((wd.y >> 1) != (e & 0x7FFFFFFFu)) {
-        if (__builtin_amdgcn_s_memrealtime() - t0 > d.wait) { late = true; break; }
-        __builtin_amdgcn_s_sleep(1);
-        wd = dload2(in);
-      }
-      v = __uint_as_float(wd.x);
-      rbad = (wd.y & 1u) != 0u;
-    }
+    if (r != d.rank) v = dp_recv(dp_slot(own, par, r, p), e, d.wait, late, rbad);
     vals[r][l] = v;
   }
   const bool anylate = __syncthreads_or(late);
   const bool anybad = __syncthreads_or(rbad) || bad;
   if (t == 0) ep[blk] = e;                    // this block's launch is consumed
   if (t >= RED_P || p >= glen) return;
-  float tot = 0.f;
-  for (int q = 0; q < d.world; ++q) tot += vals[q][l];
-  if (MODE != dpk::SUM && p == np + HDG_TR_CE && anylate) tot = __builtin_nanf("");
-  gout[p] = tot;
-  if (anylate && t == 0 && status) xstore1(status, HDG_STATUS_DP_TIMEOUT);
-  if constexpr (MODE == dpk::SUM) return;
-  const int TH1 = np - 4, TH2 = np - 2;
-  if (stats && p >= np + HDG_TR_COUNT && p <= np + HDG_TR_FAULT)   // count parts, fault
-    stats[4 + (p - np - HDG_TR_COUNT)] = tot;
-  if (p == np + HDG_TR_CE && stats) {
-    const float ce = tot * inv_pairs;
-    stats[0] = ce;
-    stats[1] = aux[1];
-    stats[2] = aux[0];
-    stats[3] = 10.f * ce + 0.1f * aux[1] + aux[0];
-  }
-  if (anylate || anybad) upd = false;
-  if (upd) {
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    const float lr_t = lr * aux[4], n1 = aux[2], n2 = aux[3];
-    float gg = tot + 0.001f * w;
-    if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w / n1;
-    if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w / n2;
-    float m = m0, v = v0;
-    m += (gg - m) * (1.f - b1);
-    v += (gg * gg - v) * (1.f - b2);
-    mm[p] = m;
-    vv[p] = v;
-    params[p] = w - lr_t * m / (sqrtf(v) + eps);
-  }
-  if (blk == 0 && t == 0 && upd) {
-    bpow[0] = aux[5];
-    bpow[1] = aux[6];
-  }
+  dp_own_slot<MODE != dpk::SUM>(vals, d.world, l, p, np, blk == 0 && t == 0, anylate, anybad,
+                                upd, w, m0, v0, gout, params, mm, vv, bpow, aux, lr, inv_pairs,
+                                stats, status);
 }
 
 // k_dp_tail's SUM / GRAD modes for ranks that share a device (hdg_dp.flags HDG_DP_SHARED):
@@ -183,7 +191,8 @@ __global__ __launch_bounds__(1024) void k_dp_tail(const float* __restrict__ src,
 // block first sends the words of all its groups (the values are src[p], the epoch of group
 // k is ep[k] + 1 as in k_dp_tail), then receives, sums and updates its groups in order:
 // the same words, tags, rank-order sums and Adam arithmetic as one k_dp_tail block per
-// group, so the two kernels give the same bits and keep the same per-group launch counters.
+// group (both call dp_recv and dp_own_slot), so the two kernels give the same bits and keep
+// the same per-group launch counters.
 // Only G blocks per rank spin, so the W-1 ranks waiting for the last one cover at most
 // half the CUs and the last rank's step kernel always finds CUs to run on.
 template <int MODE>
@@ -217,105 +226,34 @@ __global__ __launch_bounds__(DP_NT_LIGHT) void k_dp_tail_shared(
     bool upd = MODE != dpk::SUM && t < RED_P && p < np;
     const float w = upd ? params[p] : 0.f, m0 = upd ? mm[p] : 0.f, v0 = upd ? vv[p] : 0.f;
     bool late = false, rbad = false;
-    if (r < d.world && p < glen) {
-      float v;
-      if (r != d.rank) {
-        const uint32_t* in = dp_slot(own, par, r, p);
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        xu2 wd = dload2(in);
-        while ((wd.y >> 1) != (e & 0x7FFFFFFFu)) {
-          if (__builtin_amdgcn_s_memrealtime() - t0 > d.wait) { late = true; break; }
-          __builtin_amdgcn_s_sleep(1);
-          wd = dload2(in);
-        }
-        v = __uint_as_float(wd.x);
-        rbad = (wd.y & 1u) != 0u;
-      } else {
-        v = src[p];
-      }
-      vals[r][l] = v;
-    }
+    if (r < d.world && p < glen)
+      vals[r][l] =
+          r != d.rank ? dp_recv(dp_slot(own, par, r, p), e, d.wait, late, rbad) : src[p];
     const bool anylate = __syncthreads_or(late);
     const bool anybad = __syncthreads_or(rbad) || bad;
     if (t == 0) ep[k] = e;                      // this group's launch is consumed
-    if (t < RED_P && p < glen) {
-      float tot = 0.f;
-      for (int q = 0; q < d.world; ++q) tot += vals[q][l];
-      if (MODE != dpk::SUM && p == np + HDG_TR_CE && anylate) tot = __builtin_nanf("");
-      gout[p] = tot;
-      if (anylate && t == 0 && status) xstore1(status, HDG_STATUS_DP_TIMEOUT);
-      if constexpr (MODE == dpk::GRAD) {
-        const int TH1 = np - 4, TH2 = np - 2;
-        if (stats && p >= np + HDG_TR_COUNT && p <= np + HDG_TR_FAULT)
-          stats[4 + (p - np - HDG_TR_COUNT)] = tot;
-        if (p == np + HDG_TR_CE && stats) {
-          const float ce = tot * inv_pairs;
-          stats[0] = ce;
-          stats[1] = aux[1];
-          stats[2] = aux[0];
-          stats[3] = 10.f * ce + 0.1f * aux[1] + aux[0];
-        }
-        if (anylate || anybad) upd = false;
-        if (upd) {
-          const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-          const float lr_t = lr * aux[4], n1 = aux[2], n2 = aux[3];
-          float gg = tot + 0.001f * w;
-          if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w / n1;
-          if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w / n2;
-          float m = m0, v = v0;
-          m += (gg - m) * (1.f - b1);
-          v += (gg * gg - v) * (1.f - b2);
-          mm[p] = m;
-          vv[p] = v;
-          params[p] = w - lr_t * m / (sqrtf(v) + eps);
-        }
-        if (k == 0 && t == 0 && upd) {
-          bpow[0] = aux[5];
-          bpow[1] = aux[6];
-        }
-      }
-    }
+    if (t < RED_P && p < glen)
+      dp_own_slot<MODE == dpk::GRAD>(vals, d.world, l, p, np, k == 0 && t == 0, anylate, anybad,
+                                     upd, w, m0, v0, gout, params, mm, vv, bpow, aux, lr,
+                                     inv_pairs, stats, status);
     __syncthreads();                            // vals is rewritten by the next group
   }
 }
 
 // aux for MODE GRAD (k_commit_step's block 0 writes it on the fused path): loss terms of
 // the pre-update parameters (model_2.py:123-130, 326-333) and TF ApplyAdam's lr factor,
-// in k_adam_tf's summation order
+// summed by adam_sq_sums, as k_adam_tf does
 __global__ __launch_bounds__(1024) void k_dp_aux(const float* __restrict__ params, const int np,
                                                  const float* __restrict__ bpow,
                                                  float* __restrict__ aux) {
-  const int TH1 = np - 4, TH2 = np - 2;
   __shared__ float red[16 * 4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  float l2 = 0.f, t1 = 0.f, t2 = 0.f;
+  __shared__ float sh[4];
+  const int t = threadIdx.x;
+  float w[ADAM_PT];
 #pragma unroll
-  for (int u = 0; u < ADAM_PT; ++u) {
-    const int p = t + u * 1024;
-    const float w = p < np ? params[p] : 0.f;
-    l2 = fmaf(w, w, l2);
-    if (p >= TH1 && p < TH1 + 2) t1 = fmaf(w, w, t1);
-    if (p >= TH2 && p < TH2 + 2) t2 = fmaf(w, w, t2);
-  }
-  l2 = wave_sum(l2);
-  t1 = wave_sum(t1);
-  t2 = wave_sum(t2);
-  if (lane == 0) { red[wv * 4] = l2; red[wv * 4 + 1] = t1; red[wv * 4 + 2] = t2; }
-  __syncthreads();
-  if (t == 0) {
-    float s[3] = {0.f, 0.f, 0.f};
-    for (int q = 0; q < 16; ++q)
-      for (int c = 0; c < 3; ++c) s[c] += red[q * 4 + c];
-    const float n1 = sqrtf(s[1]), n2 = sqrtf(s[2]);
-    const float b1p = bpow[0], b2p = bpow[1];
-    aux[0] = 0.0005f * s[0];
-    aux[1] = 0.01f * (n2 + n1);
-    aux[2] = n1;
-    aux[3] = n2;
-    aux[4] = sqrtf(1.f - b2p) / (1.f - b1p);
-    aux[5] = b1p * 0.9f;
-    aux[6] = b2p * 0.999f;
-  }
+  for (int u = 0; u < ADAM_PT; ++u) w[u] = t + u * 1024 < np ? params[t + u * 1024] : 0.f;
+  adam_sq_sums(w, np, red, sh);
+  if (t == 0) adam_aux_store(aux, sh[0], sqrtf(sh[1]), sqrtf(sh[2]), bpow[0], bpow[1]);
 }
 
 int dp_args(const hdg_dp* dp, DpArgs& a) {

@@ -1,10 +1,13 @@
 // fused_tail.h -- the fused path's gradient layout and the deterministic reduction of the
 // step kernel's partial rows, shared by the kernels that end a fused step: k_grad_reduce /
-// k_reduce_adam / k_adam_tf (hdgnn.hip) and the data-parallel tails (dp.hip).
+// k_reduce_adam / k_adam_tf (hdgnn.hip) and the data-parallel tails (dp.hip).  What those
+// kernels do with a reduced slot (TF1 ApplyAdam, the aux block, the loss stats) is in
+// adam_tf.h, which the general path's tail (wide.hip) shares.
 #ifndef HDGNN_FUSED_TAIL_H
 #define HDGNN_FUSED_TAIL_H
 
 #include "hdgnn_internal.h"
+#include "adam_tf.h"
 
 namespace hdg {
 
@@ -28,19 +31,6 @@ HDG_M2_SAME(TH1); HDG_M2_SAME(TH2); HDG_M2_SAME(NP);
 }  // namespace m2
 constexpr int GRAD_LEN = m2::NP + HDG_TRAILER;
 constexpr int NPART = (GRAD_LEN + 3) & ~3;   // per-block partial row: NP grads + trailer
-
-// Sum over the 4 DPP rows of a wave for every lane column: lane l gets
-// v[l] + v[l^16] + v[l^32] + v[l^48] (the permlane swaps of xlane.h, same hazard handling).
-__device__ __forceinline__ float xrow_sum4(float v) {
-  float x = v, y = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-  const float s = x + y;
-  float p = s, q = s;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q));
-  return p + q;
-}
-
-__device__ __forceinline__ float wave_sum(float v) { return xrow_sum4(row16_sum<ROW_MIRROR>(v)); }
 
 // system-scope write-through store of one word (status words the host or a peer reads)
 __device__ __forceinline__ void xstore1(uint32_t* p, const uint32_t w) {
@@ -114,8 +104,6 @@ __device__ __forceinline__ void put_count(float* __restrict__ out, const uint32_
   out[1] = (float)(c >> 16);
   out[2] = 0.f;
 }
-
-constexpr int ADAM_PT = 4;   // parameters per thread: 4 x 1024 >= every variant's count
 
 }  // namespace hdg
 

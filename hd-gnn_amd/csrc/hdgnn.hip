@@ -1615,19 +1615,12 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
           *reinterpret_cast<const float4*>(pp + PL.xl + w);
   if (t == 0) { kzero[0] = 0.f; kzero[1] = 1.f; }
   __syncthreads();
-  if (aux && b == 0 && h == 0 && t == 0) {   // model_2.py:123-130, 326-333; TF ApplyAdam lr_t
-    float s2 = 0.f;
+  if (aux && b == 0 && h == 0 && t == 0) {   // adam_tf.h's aux block; the norms from two
+    float s2 = 0.f;                          // explicit products here (no fmaf chain): kept
     for (int w = 0; w < NT_MID / 64; ++w) s2 += red[w * 32];
     const float n1 = sqrtf(Ws[TH1] * Ws[TH1] + Ws[TH1 + 1] * Ws[TH1 + 1]);
     const float n2 = sqrtf(Ws[TH2] * Ws[TH2] + Ws[TH2 + 1] * Ws[TH2 + 1]);
-    const float b1p = bpow[0], b2p = bpow[1];
-    aux[0] = 0.0005f * s2;
-    aux[1] = 0.01f * (n2 + n1);
-    aux[2] = n1;
-    aux[3] = n2;
-    aux[4] = sqrtf(1.f - b2p) / (1.f - b1p);
-    aux[5] = b1p * 0.9f;
-    aux[6] = b2p * 0.999f;
+    adam_aux_store(aux, s2, n1, n2, bpow[0], bpow[1]);
   }
   MID_STAMP();
 
@@ -2698,8 +2691,7 @@ __global__ __launch_bounds__(1024) void k_grad_reduce(const float* __restrict__ 
 
 // Single-process training step tail: the reduction above fused with TF1 Adam for the
 // block's 64 parameters.  aux (written by block 0 of k_commit_step from the pre-update
-// parameters): [lpara, lmap, |theta1|, |theta2|, sqrt(1-b2^t)/(1-b1^t), b1^(t+1),
-// b2^(t+1)], so no block here depends on another.
+// parameters) is adam_tf.h's AUX_* block, so no block here depends on another.
 __global__ __launch_bounds__(1024) void k_reduce_adam(const float* __restrict__ part, int B,
                                                       float* __restrict__ params,
                                                       float* __restrict__ mm,
@@ -2714,7 +2706,7 @@ __global__ __launch_bounds__(1024) void k_reduce_adam(const float* __restrict__ 
   bool upd = threadIdx.x < RED_P && p < NP;
   // the update's operands are fetched before the reduction so both latencies overlap
   const float w = upd ? params[p] : 0.f, m0 = upd ? mm[p] : 0.f, v0 = upd ? vv[p] : 0.f;
-  const float lr_t = lr * aux[4], n1 = aux[2], n2 = aux[3];
+  const float lr_t = lr * aux[AUX_LRF], n1 = aux[AUX_N1], n2 = aux[AUX_N2];
   // split mode: any block whose pair exchange timed out voids the whole update (the rows'
   // fault slots, contiguous past the rows: k_commit_step's fsl)
   bool bad = false;
@@ -2728,40 +2720,17 @@ __global__ __launch_bounds__(1024) void k_reduce_adam(const float* __restrict__ 
   else if (p < CNT_SLOT || (p > CNT_SLOT + 2 && p < GRAD_LEN)) grad[p] = g;
   if (stats && p == CNT_SLOT) put_count(stats + 4, cnt);
   if (stats && p == NP + HDG_TR_FAULT) stats[7] = g;
-  if (p == NP) {
-    const float ce = g * inv_pairs;
-    if (stats) {
-      stats[0] = ce;
-      stats[1] = aux[1];
-      stats[2] = aux[0];
-      stats[3] = 10.f * ce + 0.1f * aux[1] + aux[0];
-    }
-  }
-  if (upd) {
-    const float b1 = 0.9f, b2 = 0.999f, ep = 1e-8f;
-    float gg = g + 0.001f * w;
-    if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w / n1;
-    if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w / n2;
-    float m = m0, v = v0;
-    m += (gg - m) * (1.f - b1);
-    v += (gg * gg - v) * (1.f - b2);
-    mm[p] = m;
-    vv[p] = v;
-    params[p] = w - lr_t * m / (sqrtf(v) + ep);
-  }
+  if (p == NP + HDG_TR_CE && stats)
+    step_stats_store(stats, g, inv_pairs, aux[AUX_LMAP], aux[AUX_LPARA]);
+  if (upd) adam_tf_slot(p, NP, g, w, m0, v0, lr_t, n1, n2, params, mm, vv);
   if (blockIdx.x == 0 && threadIdx.x == 0 && upd) {
-    bpow[0] = aux[5];
-    bpow[1] = aux[6];
+    bpow[0] = aux[AUX_B1P];
+    bpow[1] = aux[AUX_B2P];
   }
 }
 
-// ------------------------------------------------------------------------------
-// TF1 Adam (model_2.py:336-338): train_loss = 10 CE + 0.1 loss_map + loss_para.
-//   g = dCE-part (from the reduction, already x10/(B Pc)) + 0.001 v
-//       + [theta] 0.1*0.01*theta/|theta|
-//   lr_t = lr sqrt(1-b2^t)/(1-b1^t);  m += (g-m)(1-b1); v += (g^2-v)(1-b2);
-//   var -= lr_t m / (sqrt(v) + eps)     (tensorflow/core/kernels/training_ops.cc ApplyAdam)
-// ------------------------------------------------------------------------------
+// The RCCL data-parallel path's Adam after its all-reduce: adam_tf.h's aux values formed
+// in registers by one block, then every slot's update.  lr_t left to right here (adam_tf.h).
 __global__ __launch_bounds__(1024) void k_adam_tf(float* __restrict__ params,
                                                   float* __restrict__ mm,
                                                   float* __restrict__ vv,
@@ -2769,10 +2738,9 @@ __global__ __launch_bounds__(1024) void k_adam_tf(float* __restrict__ params,
                                                   const float* __restrict__ grad, int np,
                                                   float lr, float inv_pairs,
                                                   float* __restrict__ stats) {
-  const int TH1 = np - 4, TH2 = np - 2;   // map_conv thetas close every variant
   __shared__ float red[16 * 4];
   __shared__ float sh[4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int t = threadIdx.x;
   // every operand of the thread's parameters is loaded up front: one memory round trip
   float w[ADAM_PT], g[ADAM_PT], m[ADAM_PT], v[ADAM_PT];
 #pragma unroll
@@ -2787,55 +2755,22 @@ __global__ __launch_bounds__(1024) void k_adam_tf(float* __restrict__ params,
   __shared__ float bp[2];          // beta powers through LDS: only thread 0 touches bpow
   if (t == 0) { bp[0] = bpow[0]; bp[1] = bpow[1]; }
   const float ce_sum = grad[np + HDG_TR_CE], fault = grad[np + HDG_TR_FAULT];
-  float l2 = 0.f, t1 = 0.f, t2 = 0.f;
-#pragma unroll
-  for (int u = 0; u < ADAM_PT; ++u) {
-    const int p = t + u * 1024;
-    l2 = fmaf(w[u], w[u], l2);
-    if (p >= TH1 && p < TH1 + 2) t1 = fmaf(w[u], w[u], t1);
-    if (p >= TH2 && p < TH2 + 2) t2 = fmaf(w[u], w[u], t2);
-  }
-  l2 = wave_sum(l2);
-  t1 = wave_sum(t1);
-  t2 = wave_sum(t2);
-  if (lane == 0) { red[wv * 4] = l2; red[wv * 4 + 1] = t1; red[wv * 4 + 2] = t2; }
-  __syncthreads();
-  if (t < 3) {
-    float s = 0.f;
-    for (int q = 0; q < 16; ++q) s += red[q * 4 + t];
-    sh[t] = s;
-  }
-  __syncthreads();
+  adam_sq_sums(w, np, red, sh);
   const float n1 = sqrtf(sh[1]), n2 = sqrtf(sh[2]);
   const float b1p = bp[0], b2p = bp[1];
   const float lr_t = lr * sqrtf(1.f - b2p) / (1.f - b1p);
   if (t == 0 && stats) {
-    const float ce = ce_sum * inv_pairs;
-    const float lmap = 0.01f * (n2 + n1);
-    const float lpara = 0.0005f * sh[0];
-    stats[0] = ce;
-    stats[1] = lmap;
-    stats[2] = lpara;
-    stats[3] = 10.f * ce + 0.1f * lmap + lpara;
+    step_stats_store(stats, ce_sum, inv_pairs, loss_map(n1, n2), loss_para(sh[0]));
     for (int q = 0; q < 4; ++q) stats[4 + q] = grad[np + HDG_TR_COUNT + q];   // count, fault
   }
   if (fault != 0.f) return;   // a pair exchange timed out on some rank: no update
-  const float b1 = 0.9f, b2 = 0.999f, ep = 1e-8f;
 #pragma unroll
   for (int u = 0; u < ADAM_PT; ++u) {
     const int p = t + u * 1024;
     if (p >= np) break;
-    float gg = g[u] + 0.001f * w[u];
-    if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w[u] / n1;
-    if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w[u] / n2;
-    float mv = m[u], vq = v[u];
-    mv += (gg - mv) * (1.f - b1);
-    vq += (gg * gg - vq) * (1.f - b2);
-    mm[p] = mv;
-    vv[p] = vq;
-    params[p] = w[u] - lr_t * mv / (sqrtf(vq) + ep);
+    adam_tf_slot(p, np, g[u], w[u], m[u], v[u], lr_t, n1, n2, params, mm, vv);
   }
-  if (t == 0) { bpow[0] = b1p * b1; bpow[1] = b2p * b2; }
+  if (t == 0) { bpow[0] = b1p * ADAM_B1; bpow[1] = b2p * ADAM_B2; }
 }
 
 // ------------------------------------------------------------------------------
@@ -2858,7 +2793,7 @@ Work work_layout(const hdg_shape* s) {
   w.gam = take(B * NC16 * NC16);
   // one partial row per block (2 per commit split), then the rows' fault slots (2B floats)
   w.part = take(2 * B * (size_t)NPART + 2 * B);
-  w.aux = take(8);
+  w.aux = take(AUX_LEN);
   // block-pair inboxes (split mode): [B][2 halves][XSLOTS][NC16*HS] u64 (value, tag) words;
   // zero at allocation, left zero by every completed launch
   w.xch = take(2 * B * 4 * ((size_t)XSLOTS * NC16 * HS / 2) + B);   // + epochs

@@ -14,6 +14,8 @@
 //
 //   xlane.h       cross-lane / packed-math device primitives of every path
 //   fused_tail.h  the fused path's partial-row reduction, shared by hdgnn.hip and dp.hip
+//   adam_tf.h     the TF-Adam tail of every step-ending kernel (hdgnn.hip, dp.hip, wide.hip):
+//                 aux block layout and values, ApplyAdam of a slot, the loss stats
 #ifndef HDGNN_INTERNAL_H
 #define HDGNN_INTERNAL_H
 

@@ -44,6 +44,7 @@
 
 #include "hdgnn.h"
 #include "hdgnn_internal.h"
+#include "adam_tf.h"
 
 namespace hdg {
 namespace {
@@ -274,10 +275,10 @@ enum : int {
   D_EEC = 520,             // EE classifier U2'[:,1] - U2'[:,0]
   D_EECQ = 544,            // -log2(e) (U2'[:,1] - U2'[:,0])    (kw_ee_clsb: e = 2^delta')
   D_EEBQ = 564,            // -log2(e) (b2'[1] - b2'[0])
-  D_AUX = 568,             // [7] train steps: lpara, lmap, |theta1|, |theta2|,
-                           //     sqrt(1-b2^t)/(1-b1^t), b1^(t+1), b2^(t+1)  (kw_reduce_adam)
+  D_AUX = 568,             // [AUX_LEN] train steps: adam_tf.h's aux block (kw_reduce_adam)
   D_WORDS = 576
 };
+static_assert(D_AUX + AUX_LEN <= D_WORDS, "the aux block fits the derived table");
 
 // Prepared batch of the general path, per commit (words): cross-graph counts as in the
 // fused layout, then the sorted-x tables of the entity stages (k_prep_counts, kw_prep_sort):
@@ -402,7 +403,7 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float* red, float* out
 // kw_derive: weight products every phase reads (1 block)
 // ---------------------------------------------------------------------------------
 // With bpow (a training step that ends in kw_reduce_adam) also the step's loss terms and
-// Adam factors from the pre-update parameters (D_AUX; k_adam_tf's formulas), so that no
+// Adam factors from the pre-update parameters (D_AUX; adam_tf.h's aux block), so that no
 // block of the final reduce + Adam kernel depends on another.
 __device__ __forceinline__ void derive_body(const float* __restrict__ W, const Off& o, int Nc,
                                             float* __restrict__ D,
@@ -411,25 +412,12 @@ __device__ __forceinline__ void derive_body(const float* __restrict__ W, const O
   if (bpow) {
     __shared__ float red[NW * 3];
     __shared__ float tot[3];
-    const int np = o.NP, TH1 = np - 4, TH2 = np - 2;
     float v[3] = {0.f, 0.f, 0.f};
-    for (int p = t; p < np; p += NT) {
-      const float w = W[p];
-      v[0] = fmaf(w, w, v[0]);
-      if (p >= TH1 && p < TH1 + 2) v[1] = fmaf(w, w, v[1]);
-      if (p >= TH2 && p < TH2 + 2) v[2] = fmaf(w, w, v[2]);
-    }
+    for (int p = t; p < o.NP; p += NT) adam_sq_acc(p, o.NP, W[p], v[0], v[1], v[2]);
     block_sum<3>(v, red, tot);
     if (t == 0) {
       const float n1 = sqrtf(tot[1]), n2 = sqrtf(tot[2]);
-      const float b1p = bpow[0], b2p = bpow[1];
-      D[D_AUX + 0] = 0.0005f * tot[0];
-      D[D_AUX + 1] = 0.01f * (n2 + n1);
-      D[D_AUX + 2] = n1;
-      D[D_AUX + 3] = n2;
-      D[D_AUX + 4] = sqrtf(1.f - b2p) / (1.f - b1p);
-      D[D_AUX + 5] = b1p * 0.9f;
-      D[D_AUX + 6] = b2p * 0.999f;
+      adam_aux_store(D + D_AUX, tot[0], n1, n2, bpow[0], bpow[1]);
     }
   }
   const float Nc1 = (float)(Nc - 1);
@@ -4054,20 +4042,13 @@ __global__ __launch_bounds__(NT) void kw_ee_nodeb(
   WSTAMP(6, 4);
 }
 
-// ---------------------------------------------------------------------------------
-// kw_grad_reduce  grid (count): one wave per parameter p = p_begin + blockIdx.x; lanes
-// stride over the partial rows of p's segment in a fixed order, xor-butterfly total.
-// Parameters without a segment get 0 (data-independent: map_theta*, model_3's unused
-// entity-edge blocks; the trailer's fault slot: no exchanges on this path).  The correct-
-// prediction count (trailer slot HDG_TR_COUNT, exact integers per row) is summed as an
-// integer and written as the trailer's three 16-bit parts by that slot's wave.
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void kw_grad_reduce(const float* __restrict__ part, Segs sg,
-                                                     int p_begin, int np,
-                                                     float* __restrict__ out) {
-  const int p = p_begin + blockIdx.x, lane = threadIdx.x;
-  const int pc = np + HDG_TR_COUNT;
-  if (p > pc && p <= pc + 2) return;              // written by the count slot's wave
+// One lane's share of slot p's partial rows -> a, c: the rows of p's segment (no segment: 0)
+// in a fixed order, eight in flight per lane; the count slot pc as an exact integer in c,
+// every other slot in a.  Summed in locals: accumulating through the references compiles to
+// another loop.
+__device__ __forceinline__ void seg_slot_sum(const float* part, const Segs& sg, const int p,
+                                             const int pc, const int lane, float& a_out,
+                                             unsigned long long& c_out) {
   float a = 0.f;
   unsigned long long c = 0ull;
   for (int s = 0; s < sg.count; ++s) {
@@ -4090,6 +4071,27 @@ __global__ __launch_bounds__(64) void kw_grad_reduce(const float* __restrict__ p
       break;
     }
   }
+  a_out = a;
+  c_out = c;
+}
+
+// ---------------------------------------------------------------------------------
+// kw_grad_reduce  grid (count): one wave per parameter p = p_begin + blockIdx.x; lanes
+// stride over the partial rows of p's segment in a fixed order, xor-butterfly total.
+// Parameters without a segment get 0 (data-independent: map_theta*, model_3's unused
+// entity-edge blocks; the trailer's fault slot: no exchanges on this path).  The correct-
+// prediction count (trailer slot HDG_TR_COUNT, exact integers per row) is summed as an
+// integer and written as the trailer's three 16-bit parts by that slot's wave.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void kw_grad_reduce(const float* __restrict__ part, Segs sg,
+                                                     int p_begin, int np,
+                                                     float* __restrict__ out) {
+  const int p = p_begin + blockIdx.x, lane = threadIdx.x;
+  const int pc = np + HDG_TR_COUNT;
+  if (p > pc && p <= pc + 2) return;              // written by the count slot's wave
+  float a = 0.f;
+  unsigned long long c = 0ull;
+  seg_slot_sum(part, sg, p, pc, lane, a, c);
   if (p == pc) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
@@ -4105,8 +4107,8 @@ __global__ __launch_bounds__(64) void kw_grad_reduce(const float* __restrict__ p
   if (lane == 0) out[blockIdx.x] = a;
 }
 
-// kw_reduce_adam  (grid below): kw_grad_reduce fused with
-// k_adam_tf for a single-process training step (hdg_train_step on the general path and on
+// kw_reduce_adam  (grid below): kw_grad_reduce fused with TF1 Adam (adam_tf.h) for a
+// single-process training step (hdg_train_step on the general path and on
 // the model_4 fused path).  Slots in [seg_lo, seg_hi) are reduced from the partial rows as
 // in kw_grad_reduce; the others (model_4 on the fused path) from the step kernel's
 // per-block rows fp (frows rows of fstride floats, model_2 layout: slot p of the model_4
@@ -4114,7 +4116,7 @@ __global__ __launch_bounds__(64) void kw_grad_reduce(const float* __restrict__ p
 // ApplyAdam for a parameter slot, with the loss terms and the Adam factor kw_derive put in
 // D_AUX from the pre-update parameters, so no block depends on another; the CE slot's wave
 // writes the loss stats, block 0 the new beta powers.  A fault in the step kernel's rows
-// (a block-pair exchange timed out) skips every update, as in k_adam_tf.
+// (a block-pair exchange timed out) skips every update, as at every Adam site.
 
 // one slot's reduced value: the gradient out (the count slot as three 16-bit parts), the
 // stats on the CE slot, and TF1 ApplyAdam on a parameter slot
@@ -4139,28 +4141,14 @@ __device__ __forceinline__ void reduce_adam_slot(int p, int np, float g, unsigne
   }
   grad[p] = g;
   if (p == np + HDG_TR_FAULT && stats) stats[7] = g;
-  if (p == np + HDG_TR_CE && stats) {
-    const float ce = g * inv_pairs;
-    stats[0] = ce;
-    stats[1] = D[D_AUX + 1];
-    stats[2] = D[D_AUX + 0];
-    stats[3] = 10.f * ce + 0.1f * D[D_AUX + 1] + D[D_AUX + 0];
-  }
+  const float* aux = D + D_AUX;
+  if (p == np + HDG_TR_CE && stats)
+    step_stats_store(stats, g, inv_pairs, aux[AUX_LMAP], aux[AUX_LPARA]);
   if (p >= np || fault) return;
-  const float b1 = 0.9f, b2 = 0.999f, ep = 1e-8f;
-  const int TH1 = np - 4, TH2 = np - 2;
-  float gg = g + 0.001f * w;
-  if (p >= TH1 && p < TH1 + 2) gg += 0.001f * w / D[D_AUX + 2];
-  if (p >= TH2 && p < TH2 + 2) gg += 0.001f * w / D[D_AUX + 3];
-  float m = m0, v = v0;
-  m += (gg - m) * (1.f - b1);
-  v += (gg * gg - v) * (1.f - b2);
-  mm[p] = m;
-  vv[p] = v;
-  params[p] = w - (lr * D[D_AUX + 4]) * m / (sqrtf(v) + ep);
+  adam_tf_slot(p, np, g, w, m0, v0, lr * aux[AUX_LRF], aux[AUX_N1], aux[AUX_N2], params, mm, vv);
   if (p == 0) {
-    bpow[0] = D[D_AUX + 5];
-    bpow[1] = D[D_AUX + 6];
+    bpow[0] = aux[AUX_B1P];
+    bpow[1] = aux[AUX_B2P];
   }
 }
 
@@ -4233,30 +4221,7 @@ __global__ __launch_bounds__(NT) void kw_reduce_adam(
   const float w = isp ? params[p] : 0.f, m0 = isp ? mm[p] : 0.f, v0 = isp ? vv[p] : 0.f;
   float a = 0.f;
   unsigned long long c = 0ull;
-  if (live)
-    for (int q = 0; q < sg.count; ++q) {
-      const Seg& sgq = sg.s[q];
-      if (sgq.n > 0 && p >= sgq.p0 && p < sgq.p0 + sgq.n) {
-        const float* src = part + sgq.off + (long long)(p - sgq.p0) * sgq.rows;
-        constexpr int RU = 8;
-        for (int r0 = lane; r0 < sgq.rows; r0 += 64 * RU) {
-          float v[RU];
-#pragma unroll
-          for (int u = 0; u < RU; ++u) {
-            const int r = r0 + 64 * u;
-            v[u] = r < sgq.rows ? src[r] : 0.f;
-          }
-#pragma unroll
-          for (int u = 0; u < RU; ++u) {
-            if (r0 + 64 * u < sgq.rows) {
-              if (p == pc) c += (unsigned long long)v[u];
-              else a += v[u];
-            }
-          }
-        }
-        break;
-      }
-    }
+  if (live) seg_slot_sum(part, sg, p, pc, lane, a, c);
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
   const float g = wsum(a);

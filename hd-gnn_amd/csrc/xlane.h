@@ -40,6 +40,20 @@ __device__ __forceinline__ void swap16(float& x, float& y) {
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
 }
 
+// Sum over the 4 DPP rows of a wave for every lane column: lane l gets
+// v[l] + v[l^16] + v[l^32] + v[l^48] (the swaps above, same hazard handling).
+__device__ __forceinline__ float xrow_sum4(float v) {
+  float x = v, y = v;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+  const float s = x + y;
+  float p = s, q = s;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(p), "+v"(q));
+  return p + q;
+}
+
+// whole-wave sum in the fused path's lane pairing, every lane receives it
+__device__ __forceinline__ float wave_sum(float v) { return xrow_sum4(row16_sum<ROW_MIRROR>(v)); }
+
 __device__ __forceinline__ float relu(float v) { return fmaxf(v, 0.f); }
 // ln x for x in [1, 2] (the two-class CE's log(1 + e^-|d|) and log(e0 + e1)): v_log_f32
 // (log2, ~1 ulp, no denormal range to guard) times ln 2 -- 2 VALU ops where logf expands to
