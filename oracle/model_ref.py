@@ -262,16 +262,79 @@ class AdamTF:
     """Restates TF1 ApplyAdam:  lr_t = lr*sqrt(1-b2^t)/(1-b1^t);
     m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  var -= lr_t m / (sqrt(v) + eps).
     beta powers are float32 variables in TF (initialised to b1, b2 and
-    multiplied after every apply); emulated in float32 here."""
+    multiplied after every apply); emulated in float32 here.
 
-    def __init__(self, n, lr=3e-4, b1=0.9, b2=0.999, eps=1e-8):
+    exact=True is training_ops.cc's ApplyAdam to the letter: float64 arithmetic on the
+    float32 inputs with every constant at its float32 value (lr, 0.9f, 0.999f, 1e-8f, and
+    T(1) - beta formed in float32: 1.f - 0.999f lies 1.3e-5 below 0.001), the moments in
+    TF's increment form  m += (g - m)(1 - b1),  v += (g^2 - v)(1 - b2).  Then step_raw()
+    takes the gradient without the regularisers, as the engine's tail does, and adds them
+    with csrc/adam_tf.h's float32 factors.  m, v, b1p, b2p are plain attributes: set them
+    to start from any state; apply() returns (theta', m', v', b1p', b2p')."""
+
+    REG_W = np.float32(0.001)      # adam_tf.h LPARA_GRAD: d loss_para / dw
+    REG_TH = np.float32(0.001)     # adam_tf.h LMAP_GRAD: 0.1 d loss_map / d theta, x theta/|theta|
+
+    def __init__(self, n, lr=3e-4, b1=0.9, b2=0.999, eps=1e-8, exact=False):
+        self.exact = exact
+        if exact:
+            lr, b1, b2, eps = (float(np.float32(c)) for c in (lr, b1, b2, eps))
+            self.omb1 = float(np.float32(1) - np.float32(b1))
+            self.omb2 = float(np.float32(1) - np.float32(b2))
         self.lr, self.b1, self.b2, self.eps = lr, b1, b2, eps
         self.m = np.zeros(n, np.float64)
         self.v = np.zeros(n, np.float64)
         self.b1p = np.float32(b1)
         self.b2p = np.float32(b2)
 
+    @staticmethod
+    def beta_powers(t, b1=0.9, b2=0.999):
+        """(b1^t, b2^t) as TF holds them before step t >= 1: the float32 recurrence, the
+        initial value multiplied t - 1 times in float32 (0.9^t leaves the normal range at
+        t ~ 830 and then sits on a denormal; 0.9 ** t would say 0)."""
+        b1, b2 = np.float32(b1), np.float32(b2)
+        p1, p2 = b1, b2
+        for _ in range(t - 1):
+            n1, n2 = np.float32(p1 * b1), np.float32(p2 * b2)
+            if n1 == p1 and n2 == p2:          # both stuck: every later step is the same
+                break
+            p1, p2 = n1, n2
+        return p1, p2
+
+    def reg_grad(self, theta):
+        """exact mode: d(loss_para + 0.1 loss_map)/d theta with adam_tf.h's float32 factors
+        (the thetas are the vector's last four slots: theta1, theta2)."""
+        theta = np.asarray(theta, np.float64)
+        r = float(self.REG_W) * theta
+        n = len(theta)
+        for off in (n - 4, n - 2):
+            th = theta[off:off + 2]
+            r[off:off + 2] += float(self.REG_TH) * th / math.sqrt(float(th[0] * th[0] + th[1] * th[1]))
+        return r
+
+    def apply(self, theta, g):
+        """One ApplyAdam of the full gradient g -> (theta', m', v', b1p', b2p'); the state
+        advances."""
+        theta = self.step(theta, g)
+        return theta, self.m, self.v, self.b1p, self.b2p
+
+    def step_raw(self, theta, g):
+        """exact mode: apply() of g + reg_grad(theta), g being what the reduction hands the
+        engine's tail (the CE part alone)."""
+        assert self.exact
+        return self.apply(theta, np.asarray(g, np.float64) + self.reg_grad(theta))
+
     def step(self, theta, g):
+        if self.exact:
+            theta, g = np.asarray(theta, np.float64), np.asarray(g, np.float64)
+            b1p, b2p = float(self.b1p), float(self.b2p)
+            lr_t = self.lr * math.sqrt(1 - b2p) / (1 - b1p)
+            self.m = self.m + (g - self.m) * self.omb1
+            self.v = self.v + (g * g - self.v) * self.omb2
+            theta = theta - lr_t * self.m / (np.sqrt(self.v) + self.eps)
+            self.b1p = np.float32(self.b1p * np.float32(self.b1))
+            self.b2p = np.float32(self.b2p * np.float32(self.b2))
+            return theta
         lr_t = self.lr * math.sqrt(1 - float(self.b2p)) / (1 - float(self.b1p))
         self.m = self.b1 * self.m + (1 - self.b1) * g
         self.v = self.b2 * self.v + (1 - self.b2) * g * g
