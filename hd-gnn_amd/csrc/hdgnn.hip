@@ -2940,6 +2940,11 @@ int check_batch(const hdg_batch* bt) {
     return fail(HDG_EINVAL, "batch has a NULL device pointer");
   return 0;
 }
+int check_state(const hdg_state* state) {
+  if (!state || !state->params || !state->adam_m || !state->adam_v || !state->beta_pow)
+    return fail(HDG_EINVAL, "NULL state pointer");
+  return 0;
+}
 
 // Split mode (two blocks per commit, hunk rows split by parity, block-pair exchanges)
 // needs both blocks of a pair resident at once.  The host asks for it only when the
@@ -3053,16 +3058,27 @@ hipError_t launch_step(const hdg_shape* s, const hdg_batch* bt, const float* par
   return hdg::kmark("k_commit_step", st);
 }
 
+// The fused step of a shape: k_commit_step in the shape's form, and what the step's tail
+// needs of it -- the workspace layout, split mode and the partial rows it left at ws + w.part
+struct Step {
+  Work w;
+  float* ws;
+  bool split;
+  int rows;
+};
+Step step_of(const hdg_shape* s, void* workspace) {   // host queries only: nothing on a stream
+  const bool split = use_split(s);
+  return Step{work_layout(s), (float*)workspace, split, part_rows(s, split)};
+}
 template <bool TRAIN, bool STAMPS = false>
-hipError_t dispatch_step(const hdg_shape* s, const hdg_batch* bt, const float* params, float* ws,
-                         const Work& w, const StepOut& o, float ce_scale,
-                         unsigned long long* stamps, hipStream_t st, bool split,
-                         const float* bpow = nullptr, const Hyb& hy = Hyb{0, nullptr, 0, nullptr}) {
-#define HDG_STEP(SM)                                                                              \
-  return split ? launch_step<SM, TRAIN, STAMPS, true>(s, bt, params, ws, w, o, ce_scale, stamps, \
-                                                      bpow, st, hy)                               \
-               : launch_step<SM, TRAIN, STAMPS, false>(s, bt, params, ws, w, o, ce_scale, stamps,\
-                                                       bpow, st, hy)
+hipError_t run_step(const hdg_shape* s, const hdg_batch* bt, const float* params, const Step& r,
+                    const StepOut& o, float ce_scale, hipStream_t st, const float* bpow = nullptr,
+                    const Hyb& hy = Hyb{}, unsigned long long* stamps = nullptr) {
+#define HDG_STEP(SM)                                                                          \
+  return r.split ? launch_step<SM, TRAIN, STAMPS, true>(s, bt, params, r.ws, r.w, o, ce_scale, \
+                                                        stamps, bpow, st, hy)                 \
+                 : launch_step<SM, TRAIN, STAMPS, false>(s, bt, params, r.ws, r.w, o, ce_scale, \
+                                                         stamps, bpow, st, hy)
   switch (smax_c(s->nc)) {
     case 5: HDG_STEP(5);
     case 8: HDG_STEP(8);
@@ -3071,13 +3087,33 @@ hipError_t dispatch_step(const hdg_shape* s, const hdg_batch* bt, const float* p
 #undef HDG_STEP
 }
 
-// loss_E_HR of a fused forward launch: the step kernel parked G / H in gamma's slot
-hipError_t fused_ehr(const hdg_shape* s, float* ws, const Work& w, const float* params,
-                     const hdg_outputs* out, hipStream_t st) {
+// the step's partial rows summed into grad: slot p of a row lands at p, or at p + f_shift
+// from f_at on (model_4: past the entity-edge block)
+hipError_t reduce_rows(const Step& r, int f_at, int f_shift, float* grad, hipStream_t st) {
+  hipLaunchKernelGGL(k_grad_reduce, dim3((GRAD_LEN + RED_P - 1) / RED_P), dim3(1024), 0, st,
+                     r.ws + r.w.part, r.rows, 0, GRAD_LEN, f_at, f_shift, grad);
+  return hdg::kmark("k_grad_reduce", st);
+}
+
+// what follows a forward step: the CE sum of the rows -> *ce_sum, and loss_E_HR from G / H,
+// which the step kernel parked in gamma's slot (both optional)
+hipError_t forward_tail(const hdg_shape* s, const Step& r, const float* params,
+                        const hdg_outputs* out, float* ce_sum, hipStream_t st) {
+  if (ce_sum) {
+    hipLaunchKernelGGL(k_grad_reduce, dim3(1), dim3(1024), 0, st, r.ws + r.w.part, r.rows,
+                       m2::NP, m2::NP + 1, GRAD_LEN, 0, ce_sum);
+    if (hipError_t e = hdg::kmark("k_grad_reduce", st); e != hipSuccess) return e;
+  }
   if (!out || !out->ehr) return hipSuccess;
   const size_t cs = (size_t)16 * smax_c(s->nc) * 16 * smax_c(s->nc);   // NC16^2 per commit
-  return hdg::launch_ehr(ws + w.gam, ws + w.gam + (size_t)s->nc * HS, cs, s->batch, s->nc,
-                         params, s->variant, out->ehr, st);
+  const float* G = r.ws + r.w.gam;
+  return hdg::launch_ehr(G, G + (size_t)s->nc * HS, cs, s->batch, s->nc, params, s->variant,
+                         out->ehr, st);
+}
+
+// events[k] of a timed call (hdg_fwd_bwd_events); nothing without events
+hipError_t mark(void* const* events, int k, hipStream_t st) {
+  return events ? hipEventRecord((hipEvent_t)events[k], st) : hipSuccess;
 }
 
 // ---- model_4 on the fused path ("hybrid"): the entity-edge stage runs on the general
@@ -3116,53 +3152,35 @@ hdg_batch wide_half(const hdg_batch* bt, const hdg_shape* s) {
 int hybrid_run(const hdg_shape* s, const hdg_batch* bt, const float* params, float* grad,
                hdg_outputs* out, float* ce_sum, void* workspace, bool train, hipStream_t st,
                void* const* events, const hdg::WideAdam* adam = nullptr) {
-  const HybWork hw = hyb_layout(s);
-  float* ws = (float*)workspace;
-  float* wws = ws + hw.wide;
+  float* wws = (float*)workspace + hyb_layout(s).wide;   // the general path's half
   const hdg_batch bw = wide_half(bt, s);
   const int ins = hdg::param_offsets(4).H1_W1 - m2::H1_W1;   // the entity-edge block (1002)
-  auto mark = [&](int k) -> hipError_t {
-    return events ? hipEventRecord((hipEvent_t)events[k], st) : hipSuccess;
-  };
-  HIP_TRY(mark(0));
+  HIP_TRY(mark(events, 0, st));
   if (int rc = hdg::wide_ee_fwd(s, &bw, params, wws, st,
                                 adam && train ? adam->state->beta_pow : nullptr))
     return rc;
-  const Work w = work_layout(s);
-  const bool split = use_split(s);
-  const float pairs = pair_count(s);
-  const Hyb hy{ins, hdg::wide_ncpart(s, wws), hdg::wide_ncpart_tiles(s),
-               train ? hdg::wide_dn(s, wws) : nullptr};
+  const hdg::WideEE io = hdg::wide_ee_io(s, wws);
+  const Hyb hy{ins, io.ncpart, io.tiles, train ? io.dn : nullptr};
+  const Step r = step_of(s, workspace);
   if (!train) {
-    HIP_TRY(dispatch_step<false>(s, bt, params, ws, w, step_out(out), 0.f, nullptr, st, split,
-                                 nullptr, hy));
-    if (ce_sum) {
-      hipLaunchKernelGGL(k_grad_reduce, dim3(1), dim3(1024), 0, st, ws + w.part,
-                         part_rows(s, split), m2::NP, m2::NP + 1, GRAD_LEN, 0, ce_sum);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(fused_ehr(s, ws, w, params, out, st));
-    HIP_TRY(mark(1));
-    HIP_TRY(mark(2));
-    return 0;
-  }
-  HIP_TRY(dispatch_step<true>(s, bt, params, ws, w, step_out(out), 10.f / pairs, nullptr, st,
-                              split, nullptr, hy));
-  const int R = part_rows(s, split);
-  if (adam) {   // the fused rows are reduced inside the final reduce + Adam kernel
-    hdg::WideAdam ad = *adam;
-    ad.fused = hdg::FusedRows{ws + w.part, R, NPART, m2::H1_W1, ins, m2::NP,
-                              split ? ws + w.part + (size_t)R * NPART : nullptr};
-    if (int rc = hdg::wide_ee_bwd(s, &bw, params, wws, grad, st, &ad)) return rc;
+    HIP_TRY(run_step<false>(s, bt, params, r, step_out(out), 0.f, st, nullptr, hy));
+    HIP_TRY(forward_tail(s, r, params, out, ce_sum, st));
   } else {
-    // the fused rows: [0, H1_W1) in place, [H1_W1, GRAD_LEN) past the entity-edge block
-    hipLaunchKernelGGL(k_grad_reduce, dim3((GRAD_LEN + RED_P - 1) / RED_P), dim3(1024), 0, st,
-                       ws + w.part, R, 0, GRAD_LEN, m2::H1_W1, ins, grad);
-    HIP_TRY(hdg::kmark("k_grad_reduce", st));
-    if (int rc = hdg::wide_ee_bwd(s, &bw, params, wws, grad, st)) return rc;
+    HIP_TRY(run_step<true>(s, bt, params, r, step_out(out), 10.f / pair_count(s), st, nullptr,
+                           hy));
+    hdg::WideAdam ad;
+    if (adam) {   // the fused rows are reduced inside the final reduce + Adam kernel
+      const float* rows = r.ws + r.w.part;
+      ad = *adam;
+      ad.fused = hdg::FusedRows{rows, r.rows, NPART, m2::H1_W1, ins, m2::NP,
+                                r.split ? rows + (size_t)r.rows * NPART : nullptr};
+    } else {      // the fused rows: [0, H1_W1) in place, the rest past the entity-edge block
+      HIP_TRY(reduce_rows(r, m2::H1_W1, ins, grad, st));
+    }
+    if (int rc = hdg::wide_ee_bwd(s, &bw, params, wws, grad, st, adam ? &ad : nullptr)) return rc;
   }
-  HIP_TRY(mark(1));
-  HIP_TRY(mark(2));
+  HIP_TRY(mark(events, 1, st));
+  HIP_TRY(mark(events, 2, st));
   return 0;
 }
 
@@ -3235,28 +3253,20 @@ int hdg_fwd_bwd_events(const hdg_shape* s, const hdg_batch* bt, const float* par
   if (int rc = check_batch(bt)) return rc;
   if (!params || !grad || !workspace) return fail(HDG_EINVAL, "NULL params/grad/workspace");
   hipStream_t st = (hipStream_t)stream;
-  auto mark = [&](int k) -> hipError_t {
-    return events ? hipEventRecord((hipEvent_t)events[k], st) : hipSuccess;
-  };
+  if (is_hybrid(s, path))
+    return hybrid_run(s, bt, params, grad, out, nullptr, workspace, true, st, events);
   if (path == HDG_PATH_GENERAL) {
-    HIP_TRY(mark(0));
+    HIP_TRY(mark(events, 0, st));
     if (int rc = hdg::wide_run(s, bt, params, grad, out, nullptr, workspace, true, st)) return rc;
-    HIP_TRY(mark(1));
-    HIP_TRY(mark(2));
-    return 0;
+    HIP_TRY(mark(events, 1, st));
+  } else {
+    const Step r = step_of(s, workspace);
+    HIP_TRY(mark(events, 0, st));
+    HIP_TRY(run_step<true>(s, bt, params, r, step_out(out), 10.f / pair_count(s), st));
+    HIP_TRY(mark(events, 1, st));
+    HIP_TRY(reduce_rows(r, GRAD_LEN, 0, grad, st));
   }
-  if (is_hybrid(s, path)) return hybrid_run(s, bt, params, grad, out, nullptr, workspace, true, st, events);
-  const Work w = work_layout(s);
-  float* ws = (float*)workspace;
-  const bool split = use_split(s);
-  HIP_TRY(mark(0));
-  HIP_TRY(dispatch_step<true>(s, bt, params, ws, w, step_out(out), 10.f / pair_count(s), nullptr,
-                              st, split));
-  HIP_TRY(mark(1));
-  hipLaunchKernelGGL(k_grad_reduce, dim3((GRAD_LEN + RED_P - 1) / RED_P), dim3(1024), 0, st,
-                     ws + w.part, part_rows(s, split), 0, GRAD_LEN, GRAD_LEN, 0, grad);
-  HIP_TRY(hdg::kmark("k_grad_reduce", st));
-  HIP_TRY(mark(2));
+  HIP_TRY(mark(events, 2, st));
   return 0;
 }
 
@@ -3287,10 +3297,9 @@ int hdg_debug_step_stamps(const hdg_shape* s, const hdg_batch* bt, const float* 
     return fail(HDG_EINVAL, "phase stamps exist on the fused path for model_2 only");
   if (int rc = check_batch(bt)) return rc;
   if (!stamps || !workspace || !params) return fail(HDG_EINVAL, "NULL stamps/workspace/params");
-  const Work w = work_layout(s);
-  const hipError_t e = dispatch_step<true, true>(s, bt, params, (float*)workspace, w,
-                                                 step_out(nullptr), 1.f, stamps,
-                                                 (hipStream_t)stream, use_split(s));
+  const Step r = step_of(s, workspace);
+  const hipError_t e = run_step<true, true>(s, bt, params, r, step_out(nullptr), 1.f,
+                                            (hipStream_t)stream, nullptr, Hyb{}, stamps);
   HIP_TRY(e);
   return 0;
 }
@@ -3301,19 +3310,18 @@ int hdg_adam_tf(const hdg_shape* s, hdg_state* state, const float* grad, float l
   (void)path;
   if (hdg::param_offsets(s->variant).NP > ADAM_PT * 1024)
     return fail(HDG_EINVAL, "k_adam_tf holds at most %d parameters", ADAM_PT * 1024);
-  if (!state || !state->params || !state->adam_m || !state->adam_v || !state->beta_pow || !grad)
-    return fail(HDG_EINVAL, "NULL state/grad pointer");
+  if (int rc = check_state(state)) return rc;
+  if (!grad) return fail(HDG_EINVAL, "NULL grad pointer");
   hipLaunchKernelGGL(k_adam_tf, dim3(1), dim3(1024), 0, (hipStream_t)stream, state->params,
                      state->adam_m, state->adam_v, state->beta_pow, grad,
                      hdg::param_offsets(s->variant).NP, lr, 1.f / pair_count(s), stats);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(hdg::kmark("k_adam_tf", (hipStream_t)stream));
   return 0;
 }
 
 int hdg_train_step(const hdg_shape* s, const hdg_batch* bt, hdg_state* state, float lr,
                    hdg_outputs* out, float* grad, void* workspace, void* stream) {
-  if (!state || !state->params || !state->adam_m || !state->adam_v || !state->beta_pow)
-    return fail(HDG_EINVAL, "NULL state pointer");
+  if (int rc = check_state(state)) return rc;
   RESOLVE(s, path);
   if (int rc = check_batch(bt)) return rc;
   if (!grad || !workspace) return fail(HDG_EINVAL, "NULL grad/workspace");
@@ -3328,17 +3336,15 @@ int hdg_train_step(const hdg_shape* s, const hdg_batch* bt, hdg_state* state, fl
   }
   // single process, fused path: k_commit_step (+ loss stats / Adam factor from block 0),
   // then the fused deterministic reduction + TF Adam; no all-reduce point in between
-  const Work w = work_layout(s);
-  float* ws = (float*)workspace;
+  const Step r = step_of(s, workspace);
   const float pairs = pair_count(s);
-  const bool split = use_split(s);
-  HIP_TRY(dispatch_step<true>(s, bt, state->params, ws, w, step_out(out), 10.f / pairs, nullptr,
-                              st, split, state->beta_pow));
+  HIP_TRY(run_step<true>(s, bt, state->params, r, step_out(out), 10.f / pairs, st,
+                         state->beta_pow));
   hipLaunchKernelGGL(k_reduce_adam, dim3((GRAD_LEN + RED_P - 1) / RED_P), dim3(1024), 0, st,
-                     ws + w.part, part_rows(s, split), state->params, state->adam_m,
-                     state->adam_v, state->beta_pow, ws + w.aux, lr, 1.f / pairs,
-                     out ? out->stats : nullptr, grad, split ? part_rows(s, split) : 0);
-  HIP_TRY(hipGetLastError());
+                     r.ws + r.w.part, r.rows, state->params, state->adam_m, state->adam_v,
+                     state->beta_pow, r.ws + r.w.aux, lr, 1.f / pairs, out ? out->stats : nullptr,
+                     grad, r.split ? r.rows : 0);
+  HIP_TRY(hdg::kmark("k_reduce_adam", st));
   return 0;
 }
 
@@ -3352,16 +3358,9 @@ int hdg_forward(const hdg_shape* s, const hdg_batch* bt, const float* params, hd
     return hdg::wide_run(s, bt, params, nullptr, out, ce_sum, workspace, false, st);
   if (is_hybrid(s, path))
     return hybrid_run(s, bt, params, nullptr, out, ce_sum, workspace, false, st, nullptr);
-  const Work w = work_layout(s);
-  float* ws = (float*)workspace;
-  const bool split = use_split(s);
-  HIP_TRY(dispatch_step<false>(s, bt, params, ws, w, step_out(out), 0.f, nullptr, st, split));
-  if (ce_sum) {
-    hipLaunchKernelGGL(k_grad_reduce, dim3(1), dim3(1024), 0, st, ws + w.part,
-                       part_rows(s, split), m2::NP, m2::NP + 1, GRAD_LEN, 0, ce_sum);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(fused_ehr(s, ws, w, params, out, st));
+  const Step r = step_of(s, workspace);
+  HIP_TRY(run_step<false>(s, bt, params, r, step_out(out), 0.f, st));
+  HIP_TRY(forward_tail(s, r, params, out, ce_sum, st));
   return 0;
 }
 
@@ -3393,8 +3392,7 @@ int hdg_event_destroy(void* ev) {
 int hdg_train_step_dp(const hdg_shape* s, const hdg_batch* bt, hdg_state* state, float lr,
                       hdg_outputs* out, float* grad, void* workspace, const hdg_dp* dp,
                       void* stream) {
-  if (!state || !state->params || !state->adam_m || !state->adam_v || !state->beta_pow)
-    return fail(HDG_EINVAL, "NULL state pointer");
+  if (int rc = check_state(state)) return rc;
   RESOLVE(s, path);
   if (int rc = check_batch(bt)) return rc;
   if (!grad || !workspace) return fail(HDG_EINVAL, "NULL grad/workspace");
@@ -3417,15 +3415,12 @@ int hdg_train_step_dp(const hdg_shape* s, const hdg_batch* bt, hdg_state* state,
     return hdg_adam_dp(s, state, local, grad, lr, stats, status, dp, stream);
   }
   // fused path: k_commit_step (aux from block 0), then the reduction + exchange + Adam
-  const Work w = work_layout(s);
-  float* ws = (float*)workspace;
+  const Step r = step_of(s, workspace);
   const float pairs = pair_count(s);
-  const bool split = use_split(s);
-  HIP_TRY(dispatch_step<true>(s, bt, state->params, ws, w, step_out(out), 10.f / pairs, nullptr,
-                              st, split, state->beta_pow));
-  return hdg::launch_dp_tail_part(dp, ws + w.part, part_rows(s, split),
-                                  split ? part_rows(s, split) : 0, grad, state, ws + w.aux, lr,
-                                  1.f / pairs, stats, status, st);
+  HIP_TRY(run_step<true>(s, bt, state->params, r, step_out(out), 10.f / pairs, st,
+                         state->beta_pow));
+  return hdg::launch_dp_tail_part(dp, r.ws + r.w.part, r.rows, r.split ? r.rows : 0, grad, state,
+                                  r.ws + r.w.aux, lr, 1.f / pairs, stats, status, st);
 }
 
 }  // extern "C"

@@ -5,7 +5,9 @@
 //                           model_2 with ne <= 256, nc <= 160 (the benchmark shape); path
 //                           resolution, sizing and the step entry points
 //   general path wide.hip   any ne / nc, model variants 1-4, one phase per launch with
-//                           many 256-thread blocks per commit, state in HBM
+//                           many 256-thread blocks per commit, state in HBM; on the host one
+//                           step context (WideCtx) and one launcher per launch group, which
+//                           wide_run and the model_4 halves around the fused kernel share
 //   batch prep   prep.hip   the parameter-independent tables of an uploaded batch
 //   dp tail      dp.hip     the data-parallel tail over xGMI and its mailbox API
 //   evaluation   eval.hip   on-device confusion counts and ROC-AUC
@@ -153,21 +155,24 @@ int wide_run(const hdg_shape* s, const hdg_batch* bt, const float* params, float
              hdg_outputs* out, float* ce_sum, void* workspace, bool train, hipStream_t st,
              const WideAdam* adam = nullptr);
 // model_4 on the fused path: the entity-edge stage on the general path's kernels around
-// the fused step kernel.  wide_ee_fwd: EE first layer, node products, classifier over the
-// mapped relations -> per-tile partial bins (wide_ncpart: u64 [B][wide_ncpart_tiles][Nc][2],
-// 2^-32 fixed point) of n_c[2:4] of marshalling_B2 (model_4.py:95-97), which the step kernel
-// sums;
-// wide_ee_bwd: from dn (wide_dn, [B][Nc][4], written by the step kernel) the EE backward
-// and the reduction of the EE parameters' gradient rows into grad[EE_W11 .. EC_B2 + 2).
+// the fused step kernel: wide_run's launchers with the entity stage off and the entity-edge
+// stage on.  wide_ee_fwd: EE first layer, node products, classifier over the mapped
+// relations -> per-tile partial bins (WideEE::ncpart) of n_c[2:4] of marshalling_B2
+// (model_4.py:95-97), which the step kernel sums;
+// wide_ee_bwd: from dn (WideEE::dn, written by the step kernel) the EE backward and the
+// reduction of the EE parameters' gradient rows into grad[EE_W11 .. EC_B2 + 2).
 // bt->prep, workspace: this path's layouts (wide_prep_bytes / wide_workspace_bytes).
-float* wide_dn(const hdg_shape* s, void* workspace);
 // bpow (a step ending in wide_ee_bwd with adam): the Adam factors' beta powers.
 // wide_ee_bwd with adam: every parameter's TF-Adam update in its final reduction, the
-// non-entity-edge gradients read from grad (the fused kernel's reduction wrote them).
+// non-entity-edge slots from the step kernel's rows (adam->fused).
+struct WideEE {                        // what the two halves exchange with the step kernel
+  const unsigned long long* ncpart;    // u64 [B][tiles][Nc][2], 2^-32 fixed point
+  int tiles;
+  float* dn;                           // [B][Nc][4]
+};
+WideEE wide_ee_io(const hdg_shape* s, void* workspace);
 int wide_ee_fwd(const hdg_shape* s, const hdg_batch* bt, const float* params, void* workspace,
                 hipStream_t st, const float* bpow = nullptr);
-const unsigned long long* wide_ncpart(const hdg_shape* s, void* workspace);
-int wide_ncpart_tiles(const hdg_shape* s);
 int wide_ee_bwd(const hdg_shape* s, const hdg_batch* bt, const float* params, void* workspace,
                 float* grad, hipStream_t st, const WideAdam* adam = nullptr);
 

@@ -4369,16 +4369,6 @@ __global__ __launch_bounds__(1024) void kw_prep_order(const int32_t* __restrict_
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
-bool has_ee(int v);
-bool hunk_lists(const hdg_shape* s);
-bool has_ent(int v);
-// the prep words before the entity-edge order table (= the whole prep without model_4)
-size_t ee_order_off(const hdg_shape* s) {
-  const size_t B = s->batch, WE = (s->ne + 31) / 32, WC = (s->nc + 31) / 32;
-  if (hunk_lists(s)) return ylist_layout(s->batch, s->ne, s->nc, has_ent(s->variant)).end;
-  if (has_ent(s->variant)) return list_layout(s->batch, s->ne, s->nc).end;
-  return B * gen_prep(s->ne, s->nc).words + B * s->ne * WE + B * s->nc * WC;
-}
 struct WideWork {
   size_t xp, ov, P, Eb, hE, rhoE;                 // entity stage   [B][Ne](*H)
   size_t R1, C1, Rn, Cn, rho, gmm, drho, dgam, phi, psi;   // EE     [B][Ne][H]
@@ -4389,8 +4379,7 @@ struct WideWork {
   size_t tab;                                     // f64 scan tables [2][B][H][2][Ne+1]
   size_t hsv, hsp, hsx, hsw;                      // sorted hunk tables (hunk_sorted)
   size_t htr, htc, hty;                           // one-sweep tile partials (hunk_tiled)
-  size_t part;                                    // partial rows
-  Segs segs;
+  Segs segs;                                      // partial rows: absolute float offsets
   size_t total;
 };
 
@@ -4414,7 +4403,15 @@ bool hunk_sorted(const hdg_shape* s) {
 bool hunk_lists(const hdg_shape* s) { return hdg_resolve_path(s) == HDG_PATH_GENERAL; }
 
 bool has_ent(int v) { return v == 2 || v == 4; }
-bool has_ee(int v) { return v == 4; }
+bool has_ee(int v) { return v == 4; }   // implies has_ent: model_4 is model_2 + the EE stage
+
+// the prep words before the entity-edge order table (= the whole prep without model_4)
+size_t ee_order_off(const hdg_shape* s) {
+  const size_t B = s->batch, WE = (s->ne + 31) / 32, WC = (s->nc + 31) / 32;
+  if (hunk_lists(s)) return ylist_layout(s->batch, s->ne, s->nc, has_ent(s->variant)).end;
+  if (has_ent(s->variant)) return list_layout(s->batch, s->ne, s->nc).end;
+  return B * gen_prep(s->ne, s->nc).words + B * s->ne * WE + B * s->nc * WC;
+}
 
 WideWork wide_layout(const hdg_shape* s) {
   WideWork w;
@@ -4485,16 +4482,16 @@ WideWork wide_layout(const hdg_shape* s) {
     seg(SG_EEW11, o.EE_W11, 80, re);
   }
   w.segs.count = SG_COUNT;
-  w.part = 0;   // segment offsets are absolute (floats from the workspace base)
   w.total = off;
   return w;
 }
 
-#define WTRY(expr)                                                                        \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) return fail((int)e_, "%s: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
+// the device's CU count (hdg::cu_count, asked once); `fallback` where it cannot be read
+int cus_or(int fallback) {
+  static int cus = -1;
+  if (cus < 0) cus = cu_count();
+  return cus > 0 ? cus : fallback;
+}
 
 // kw_first_bwd's form by its grid: the 512-thread blocks (3 per CU at 76 VGPRs) while they
 // fit one round, the 256-thread blocks (whole lists per wave) beyond
@@ -4503,14 +4500,7 @@ WideWork wide_layout(const hdg_shape* s) {
 #endif
 int first_bwd_halves(long long blocks) {
   if (HDG_FB_HALVES) return HDG_FB_HALVES;
-  static int cus = -1;
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-              ? n : 256;
-  }
-  return blocks > 3LL * cus ? 1 : 2;
+  return blocks > 3LL * cus_or(256) ? 1 : 2;
 }
 
 // kw_ent_fwd's form by its grid: 8 waves per block (2 blocks per CU at 126 VGPRs) while the
@@ -4520,49 +4510,29 @@ int first_bwd_halves(long long blocks) {
 #endif
 int ent_fwd_halves(long long blocks) {
   if (HDG_EF_HALVES) return HDG_EF_HALVES;
-  static int cus = -1;
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-              ? n : 256;
-  }
-  return blocks <= 2LL * cus ? 2 : 1;
+  return blocks <= 2LL * cus_or(256) ? 2 : 1;
 }
 
 int set_wide_attrs() {
   static bool attr_set = false;   // > 64 KiB of dynamic LDS for Ne > 4000
-  if (!attr_set) {
-    WTRY(hipFuncSetAttribute((const void*)kw_ent_fwd<1>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_ent_fwd<2>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_first_bwd<2>,    // + 15 KiB static hand-over
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_first_bwd<1>,    // + 15 KiB static hand-over
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_ee_fwd<1, NWP>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_ee_fwd<2, HDG_EEF_WAVES>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_ee_fwd<0, HDG_EEF_WAVES>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_ee_clsb,      // 41 KiB static + 32 KiB at Ne 4096
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    WTRY(hipFuncSetAttribute((const void*)kw_hunk_fwd_s,
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)hs_lds_bytes(HS_ALL_MAX, 1)));
-    WTRY(hipFuncSetAttribute((const void*)kw_hunk_mlpb_s,
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)hs_lds_bytes(HS_ALL_MAX, 2)));
-    WTRY(hipFuncSetAttribute((const void*)kw_hunk_fwd_g,
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)hs_lds_bytes(HS_NC_MAX, 1)));
-    WTRY(hipFuncSetAttribute((const void*)kw_hunk_mlpb_g,
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)hs_lds_bytes(HS_NC_MAX, 2)));
-    attr_set = true;
-  }
+  if (attr_set) return 0;
+  auto dyn_lds = [](auto* kernel, size_t bytes) {
+    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes);
+  };
+  HIP_TRY(dyn_lds(kw_ent_fwd<1>, 96 * 1024));
+  HIP_TRY(dyn_lds(kw_ent_fwd<2>, 96 * 1024));
+  HIP_TRY(dyn_lds(kw_first_bwd<2>, 112 * 1024));   // + 15 KiB static hand-over
+  HIP_TRY(dyn_lds(kw_first_bwd<1>, 112 * 1024));   // + 15 KiB static hand-over
+  HIP_TRY(dyn_lds((kw_ee_fwd<1, NWP>), 160 * 1024));
+  HIP_TRY(dyn_lds((kw_ee_fwd<2, HDG_EEF_WAVES>), 160 * 1024));
+  HIP_TRY(dyn_lds((kw_ee_fwd<0, HDG_EEF_WAVES>), 96 * 1024));
+  HIP_TRY(dyn_lds(kw_ee_clsb, 96 * 1024));         // 41 KiB static + 32 KiB at Ne 4096
+  HIP_TRY(dyn_lds(kw_hunk_fwd_s, hs_lds_bytes(HS_ALL_MAX, 1)));
+  HIP_TRY(dyn_lds(kw_hunk_mlpb_s, hs_lds_bytes(HS_ALL_MAX, 2)));
+  HIP_TRY(dyn_lds(kw_hunk_fwd_g, hs_lds_bytes(HS_NC_MAX, 1)));
+  HIP_TRY(dyn_lds(kw_hunk_mlpb_g, hs_lds_bytes(HS_NC_MAX, 2)));
+  attr_set = true;
   return 0;
 }
 
@@ -4572,132 +4542,318 @@ int set_wide_attrs() {
 #define HDG_EE_SNAKE 1
 #endif
 int ee_snake(const hdg_shape* s) {
-  static int cus = -1;
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-              ? n : 0;
-  }
-  return (HDG_EE_SNAKE && (long long)ee_fwd_tiles(s->ne) * s->batch <= EE_ORDER_MAX) ? cus : 0;
+  return (HDG_EE_SNAKE && (long long)ee_fwd_tiles(s->ne) * s->batch <= EE_ORDER_MAX) ? cus_or(0)
+                                                                                      : 0;
 }
 size_t ee_clsb_lds(int Ne) { return (size_t)(Ne + TB * ((Ne + 31) / 32)) * 4; }   // Eq | a^T words
 
-// kw_ee_fwd over the batch: both LDS tables up to EE_TAB_LDS_MAX nodes, the gam table alone
-// while it fits the LDS, HBM reads beyond
-int ee_snake(const hdg_shape* s);
-size_t ee_order_off(const hdg_shape* s);
-int launch_ee_fwd(const hdg_shape* s, const hdg_batch* bt, const float* params, const float* D,
-                  const float* rho, const float* gmm, unsigned long long* ncpart, hipStream_t st) {
-  const int B = s->batch, Ne = s->ne, Nc = s->nc;
-  const Off o = param_offsets(s->variant);
-  const dim3 grid(ee_fwd_tiles(Ne), B);
-  const int tm = ee_fwd_mode(Ne, Nc);
-  const int snake = ee_snake(s);
-  const uint32_t* sorder = (const uint32_t*)bt->prep + ee_order_off(s) + ((B + 3) & ~3);
-  if (tm == 1)
-    hipLaunchKernelGGL((kw_ee_fwd<1, NWP>), grid, dim3(NTP), ee_fwd_lds(Ne, Nc), st, bt->abits,
-                       bt->hid, bt->nlen, params, o, D, Ne, Nc, rho, gmm, ncpart, snake, sorder);
-  else if (tm == 2)
-    hipLaunchKernelGGL((kw_ee_fwd<2, HDG_EEF_WAVES>), grid, dim3(64 * HDG_EEF_WAVES),
-                       ee_fwd_lds(Ne, Nc), st, bt->abits, bt->hid, bt->nlen, params, o, D, Ne,
-                       Nc, rho, gmm, ncpart, snake, sorder);
-  else
-    hipLaunchKernelGGL((kw_ee_fwd<0, HDG_EEF_WAVES>), grid, dim3(64 * HDG_EEF_WAVES),
-                       ee_fwd_lds(Ne, Nc), st, bt->abits, bt->hid, bt->nlen, params, o, D, Ne,
-                       Nc, rho, gmm, ncpart, snake, sorder);
-  WTRY(kmark("kw_ee_fwd", st));
-  return 0;
+// which kernels run the hunk relu / mask sums of a shape (hunk_sorted / hunk_tiled above,
+// hs_all_shape for the sorted form's block shape)
+enum HunkForm { HF_DENSE, HF_SORTED_ALL, HF_SORTED_GROUP, HF_TILED };
+HunkForm hunk_form(const hdg_shape* s) {
+  if (hunk_sorted(s)) return hs_all_shape(s) ? HF_SORTED_ALL : HF_SORTED_GROUP;
+  return hunk_tiled(s) ? HF_TILED : HF_DENSE;
 }
+
+// f(std::integral_constant<int, E>) for the block sort's E of this Nc (hsort_e)
+template <class Fn>
+void with_hsort_e(int Nc, Fn&& f) {
+  switch (hsort_e(Nc)) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+
+// A step on this path: what every launch reads (the shape's scalars, the parameter offsets,
+// the workspace and prep layouts and the pointers into them), built once per entry point,
+// and one launcher per launch group.  (ent, ee): which of the entity and entity-edge stages
+// the call runs.  wide_run passes (has_ent, has_ee), so never (false, true); that
+// combination is wide_ee_fwd / wide_ee_bwd, where the fused step kernel runs the entity
+// stage itself.
+struct WideCtx {
+  const hdg_shape* s;
+  const hdg_batch* bt;
+  const float* params;
+  hipStream_t st;
+  const int B, Ne, Nc, v, te, tc;       // te / tc: TN-node tiles per commit
+  const Off o;
+  const WideWork w;
+  float *const ws, *const D, *const part;   // part = ws: the segment offsets are absolute
+  const uint32_t *prep, *aT, *yT;       // the batch's tables, a^T bits, y^T bits
+  const HunkForm hf;
+  const ListLayout YL;
+  const HTileSums hts;
+  float* F(size_t off) const { return ws + off; }
+
+  WideCtx(const hdg_shape* s_, const hdg_batch* bt_, const float* params_, void* workspace,
+          hipStream_t st_)
+      : s(s_), bt(bt_), params(params_), st(st_), B(s->batch), Ne(s->ne), Nc(s->nc),
+        v(s->variant), te((Ne + TN - 1) / TN), tc((Nc + TN - 1) / TN), o(param_offsets(v)),
+        w(wide_layout(s)), ws((float*)workspace), D(ws + w.D), part(ws),
+        prep((const uint32_t*)bt->prep), aT(prep + (size_t)B * gen_prep(Ne, Nc).words),
+        yT(aT + (size_t)B * Ne * ((Ne + 31) / 32)), hf(hunk_form(s)),
+        YL(ylist_layout(B, Ne, Nc, has_ent(v))),
+        hts{F(w.htr), F(w.htc), F(w.hty), (Nc + hunk_tile_cols() - 1) / hunk_tile_cols(),
+            (Nc + hunk_tile_rows() - 1) / hunk_tile_rows()} {}
+
+  // kw_ent_fwd (+ kw_derive's work in one more block column, node_fwd_tile per tile)
+  int ent_fwd(bool ent, bool ee, const float* bpow) const {
+    const NodeFwdOut no{F(w.Eb), F(w.hE), F(w.ov), F(w.xp), F(w.Rn), F(w.Cn), F(w.rho),
+                        F(w.gmm)};
+    const int ez = (ent && ee) ? 2 : 1;
+    const size_t tlds = sort_lds_bytes(Ne);
+    if (ent_fwd_halves((long long)te * B * ez) == 2)
+      hipLaunchKernelGGL(kw_ent_fwd<2>, dim3(te + 1, B, ez), dim3(NTP), tlds, st, bt->x,
+                         bt->abits, aT, prep, params, o, Ne, Nc, ent ? 1 : 0, F(w.P), F(w.R1),
+                         F(w.C1), D, bpow, no);
+    else
+      hipLaunchKernelGGL(kw_ent_fwd<1>, dim3(te + 1, B, ez), dim3(NT), tlds, st, bt->x,
+                         bt->abits, aT, prep, params, o, Ne, Nc, ent ? 1 : 0, F(w.P), F(w.R1),
+                         F(w.C1), D, bpow, no);
+    HIP_TRY(kmark("kw_ent_fwd", st));
+    return 0;
+  }
+
+  // kw_ee_fwd over the batch: both LDS tables up to EE_TAB_LDS_MAX nodes, the gam table
+  // alone while it fits the LDS, HBM reads beyond
+  int ee_fwd() const {
+    const dim3 grid(ee_fwd_tiles(Ne), B);
+    const int tm = ee_fwd_mode(Ne, Nc);
+    const int snake = ee_snake(s);
+    const uint32_t* sorder = prep + ee_order_off(s) + ((B + 3) & ~3);
+    const float *rho = F(w.rho), *gmm = F(w.gmm);
+    unsigned long long* ncpart = (unsigned long long*)F(w.ncpart);
+    if (tm == 1)
+      hipLaunchKernelGGL((kw_ee_fwd<1, NWP>), grid, dim3(NTP), ee_fwd_lds(Ne, Nc), st, bt->abits,
+                         bt->hid, bt->nlen, params, o, D, Ne, Nc, rho, gmm, ncpart, snake, sorder);
+    else if (tm == 2)
+      hipLaunchKernelGGL((kw_ee_fwd<2, HDG_EEF_WAVES>), grid, dim3(64 * HDG_EEF_WAVES),
+                         ee_fwd_lds(Ne, Nc), st, bt->abits, bt->hid, bt->nlen, params, o, D, Ne,
+                         Nc, rho, gmm, ncpart, snake, sorder);
+    else
+      hipLaunchKernelGGL((kw_ee_fwd<0, HDG_EEF_WAVES>), grid, dim3(64 * HDG_EEF_WAVES),
+                         ee_fwd_lds(Ne, Nc), st, bt->abits, bt->hid, bt->nlen, params, o, D, Ne,
+                         Nc, rho, gmm, ncpart, snake, sorder);
+    HIP_TRY(kmark("kw_ee_fwd", st));
+    return 0;
+  }
+
+  // the hunk relu sums G / H and the classifier's first layer sigma / tau
+  int hunk_fwd() const {
+    if (hf == HF_SORTED_ALL || hf == HF_SORTED_GROUP) {
+      with_hsort_e(Nc, [&](auto e) {
+        hipLaunchKernelGGL(kw_hunk_sort<decltype(e)::value>, dim3(H, B, 2), dim3(NT), 0, st,
+                           F(w.alpha), F(w.beta), Nc, F(w.hsv), (int*)F(w.hsp),
+                           (double*)F(w.hsx));
+      });
+      HIP_TRY(kmark("kw_hunk_sort", st));
+    }
+    if (hf == HF_SORTED_ALL) {
+      hipLaunchKernelGGL(kw_hunk_fwd_s, dim3((Nc + HSN - 1) / HSN, B, 2), dim3(HS_NT),
+                         hs_shape_lds_bytes(s, 1), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
+                         F(w.hsv), (const double*)F(w.hsx), prep, YL, F(w.G), F(w.Hh),
+                         F(w.sig), F(w.tau));
+      HIP_TRY(kmark("kw_hunk_fwd_s", st));
+    } else if (hf == HF_SORTED_GROUP) {
+      hipLaunchKernelGGL(kw_hunk_fwd_g, dim3(4 * hs_tiles(Nc), B, 2), dim3(NT),
+                         hs_shape_lds_bytes(s, 1), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
+                         F(w.hsv), (const double*)F(w.hsx), prep, YL, F(w.G), F(w.Hh));
+      HIP_TRY(kmark("kw_hunk_fwd_g", st));
+      hipLaunchKernelGGL(kw_hunk_sig, dim3(tc, B, 2), dim3(NT), 0, st, D, Nc, F(w.G), F(w.Hh),
+                         F(w.sig), F(w.tau));
+      HIP_TRY(kmark("kw_hunk_sig", st));
+    } else if (hf == HF_TILED) {
+      HTileArgs ha{Nc, F(w.alpha), F(w.beta), nullptr, nullptr, nullptr, D + D_DLT, bt->ybits,
+                   F(w.htr), F(w.htc), F(w.hty)};
+      HIP_TRY(launch_hunk_tile(0, ha, B, st));
+      hipLaunchKernelGGL(kw_hunk_fin0, dim3(tc, B, 2), dim3(NTP), 0, st, hts, D, Nc, F(w.alpha),
+                         F(w.beta), F(w.G), F(w.Hh), F(w.sig), F(w.tau));
+      HIP_TRY(kmark("kw_hunk_fin0", st));
+    } else {
+      hipLaunchKernelGGL(kw_hunk_fwd, dim3(tc, B, 2), dim3(NTP), 0, st, bt->ybits, yT, D, Nc,
+                         F(w.alpha), F(w.beta), F(w.G), F(w.Hh), F(w.sig), F(w.tau));
+      HIP_TRY(kmark("kw_hunk_fwd", st));
+    }
+    return 0;
+  }
+
+  // the classifier backward's mask sums: the one-sweep tiles, or the two-pass kernel of the
+  // dense and sorted forms (gprobs: gamma rebuilt from the probabilities, wide_run)
+  int hunk_clsb(const float* gprobs, float ce_scale) const {
+    if (hf == HF_TILED) {
+      HTileArgs ha{Nc, F(w.sig), F(w.tau), nullptr, nullptr, F(w.gam), D + D_EPS, bt->ybits,
+                   F(w.htr), F(w.htc), F(w.hty)};
+      HIP_TRY(launch_hunk_tile(2, ha, B, st));
+      hipLaunchKernelGGL(kw_hunk_fin2, dim3(tc, B, 2), dim3(NTP), 0, st, hts, params, o, D, Nc,
+                         F(w.G), F(w.Hh), F(w.Dsig), F(w.Dtau), F(w.dG), F(w.dH), part, w.segs);
+      HIP_TRY(kmark("kw_hunk_fin2", st));
+    } else {
+      hipLaunchKernelGGL(kw_hunk_clsb, dim3(tc, B, 2), dim3(NTP), 0, st, bt->ybits, yT, params, o,
+                         D, Nc, F(w.sig), F(w.tau), F(w.gam), F(w.G), F(w.Hh), F(w.Dsig),
+                         F(w.Dtau), F(w.dG), F(w.dH), part, w.segs, gprobs, ce_scale);
+      HIP_TRY(kmark("kw_hunk_clsb", st));
+    }
+    return 0;
+  }
+
+  // the hunk MLP backward's weighted mask sums -> D alpha / D beta, the MLP's gradient rows
+  int hunk_mlpb() const {
+    if (hf == HF_SORTED_ALL || hf == HF_SORTED_GROUP) {
+      with_hsort_e(Nc, [&](auto e) {
+        hipLaunchKernelGGL(kw_hunk_wsum<decltype(e)::value>, dim3(H, B, 2), dim3(NT), 0, st,
+                           (const int*)F(w.hsp), F(w.dG), F(w.dH), Nc, (double*)F(w.hsw));
+      });
+      HIP_TRY(kmark("kw_hunk_wsum", st));
+    }
+    if (hf == HF_SORTED_ALL) {
+      hipLaunchKernelGGL(kw_hunk_mlpb_s, dim3((Nc + HSN - 1) / HSN, B, 2), dim3(HS_NT),
+                         hs_shape_lds_bytes(s, 2), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
+                         F(w.dG), F(w.dH), F(w.nvec), F(w.hsv), (const double*)F(w.hsw), prep,
+                         YL, F(w.Dal), F(w.Dbe), part, w.segs);
+      HIP_TRY(kmark("kw_hunk_mlpb_s", st));
+    } else if (hf == HF_SORTED_GROUP) {
+      hipLaunchKernelGGL(kw_hunk_mlpb_g, dim3(4 * hs_tiles(Nc), B, 2), dim3(NT),
+                         hs_shape_lds_bytes(s, 2), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
+                         F(w.dG), F(w.dH), F(w.nvec), F(w.hsv), (const double*)F(w.hsw), prep,
+                         YL, F(w.Dal), F(w.Dbe), part, w.segs);
+      HIP_TRY(kmark("kw_hunk_mlpb_g", st));
+    } else if (hf == HF_TILED) {
+      HTileArgs ha{Nc, F(w.alpha), F(w.beta), F(w.dG), F(w.dH), nullptr, D + D_DLT, bt->ybits,
+                   F(w.htr), F(w.htc), F(w.hty)};
+      HIP_TRY(launch_hunk_tile(1, ha, B, st));
+      hipLaunchKernelGGL(kw_hunk_fin1, dim3(tc, B, 2), dim3(NTP), 0, st, hts, D, Nc, F(w.alpha),
+                         F(w.beta), F(w.dG), F(w.dH), F(w.nvec), F(w.Dal), F(w.Dbe), part, w.segs);
+      HIP_TRY(kmark("kw_hunk_fin1", st));
+    } else {
+      hipLaunchKernelGGL(kw_hunk_mlpb, dim3(tc, B, 2), dim3(NTP), 0, st, bt->ybits, yT, D, Nc,
+                         F(w.alpha), F(w.beta), F(w.dG), F(w.dH), F(w.nvec), F(w.Dal), F(w.Dbe),
+                         part, w.segs);
+      HIP_TRY(kmark("kw_hunk_mlpb", st));
+    }
+    return 0;
+  }
+
+  // the entity-edge backward from dn: the classifier over the mapped relations, the nodes
+  int ee_bwd() const {
+    hipLaunchKernelGGL(kw_ee_clsb, dim3(ee_bwd_tiles(Ne), B, 1), dim3(NT), ee_clsb_lds(Ne), st,
+                       aT, bt->hid, bt->nlen, D, Ne, Nc, ee_snake(s), prep + ee_order_off(s),
+                       F(w.rho), F(w.gmm), F(w.dn), F(w.drho), F(w.dgam), part, w.segs);
+    HIP_TRY(kmark("kw_ee_clsb", st));
+    hipLaunchKernelGGL(kw_ee_nodeb, dim3(te, B), dim3(NT), 0, st, params, o, D, Ne,
+                       ee_bwd_tiles(Ne), bt->nlen, F(w.R1), F(w.C1), F(w.Rn), F(w.Cn), F(w.drho),
+                       F(w.dgam), F(w.phi), F(w.psi), part, w.segs);
+    HIP_TRY(kmark("kw_ee_nodeb", st));
+    return 0;
+  }
+
+  // the first-layer backward of the stages this call runs: one scan, one launch
+  int first_bwd(bool ent, bool ee) const {
+    const int mode0 = ent ? 0 : 1, stages = (ent && ee) ? 2 : 1;
+    const float* rhoE = ent ? F(w.rhoE) : nullptr;
+    const size_t tlds = sort_lds_bytes(Ne);
+    hipLaunchKernelGGL(kw_scan, dim3(H, B, stages), dim3(NT), 0, st, prep, params, o, Ne, Nc,
+                       mode0, rhoE, F(w.psi), (double*)F(w.tab));
+    HIP_TRY(kmark("kw_scan", st));
+    if (first_bwd_halves((long long)te * B * stages) == 2)
+      hipLaunchKernelGGL(kw_first_bwd<2>, dim3(te, B, stages), dim3(NTP), tlds, st, bt->x,
+                         bt->abits, prep, params, o, Ne, Nc, mode0, rhoE, F(w.phi), F(w.psi),
+                         (const double*)F(w.tab), part, w.segs);
+    else
+      hipLaunchKernelGGL(kw_first_bwd<1>, dim3(te, B, stages), dim3(NT), tlds, st, bt->x,
+                         bt->abits, prep, params, o, Ne, Nc, mode0, rhoE, F(w.phi), F(w.psi),
+                         (const double*)F(w.tab), part, w.segs);
+    HIP_TRY(kmark("kw_first_bwd", st));
+    return 0;
+  }
+
+  // ---- wide_run's own stages ----
+  int derive(const float* bpow) const {
+    hipLaunchKernelGGL(kw_derive, dim3(1), dim3(NT), 0, st, params, o, Nc, D, bpow);
+    HIP_TRY(kmark("kw_derive", st));
+    return 0;
+  }
+  int cross_fwd(bool ent, bool ee) const {
+    hipLaunchKernelGGL(kw_cross_fwd, dim3((Nc + NW - 1) / NW, B), dim3(NT), 0, st, prep,
+                       ent ? F(w.xp) : bt->x, params, o, Ne, Nc,
+                       ee ? (unsigned long long*)F(w.ncpart) : nullptr, ee_fwd_tiles(Ne),
+                       F(w.nvec), F(w.alpha), F(w.beta));
+    HIP_TRY(kmark("kw_cross_fwd", st));
+    return 0;
+  }
+  template <bool TRAIN>
+  int hunk_cls(const hdg_outputs* out, float ce_scale, int gam_out) const {
+    hipLaunchKernelGGL(kw_hunk_cls<TRAIN>, dim3(tc, B, CLS_SPLIT), dim3(NTP), 0, st, yT, params, o,
+                       D, Nc, F(w.sig), F(w.tau), out ? out->probs : nullptr,
+                       out ? out->logits : nullptr, F(w.gam), ce_scale, part, w.segs, gam_out);
+    HIP_TRY(kmark("kw_hunk_cls", st));
+    return 0;
+  }
+  int dn() const {   // kw_ee_clsb reads dn; with the entity stage alone kw_node_bwd forms it
+    hipLaunchKernelGGL(kw_dn, dim3(tc, B), dim3(NT), 0, st, params, o, Nc, F(w.Dal), F(w.Dbe),
+                       F(w.dn));
+    HIP_TRY(kmark("kw_dn", st));
+    return 0;
+  }
+  int node_bwd(bool ee) const {
+    hipLaunchKernelGGL(kw_node_bwd, dim3(te, B), dim3(NT), 0, st, prep, bt->x, params, o, Ne, Nc,
+                       ee ? F(w.dn) : nullptr, F(w.ov), F(w.P), F(w.Eb), F(w.hE), F(w.rhoE), part,
+                       w.segs, F(w.Dal), F(w.Dbe));
+    HIP_TRY(kmark("kw_node_bwd", st));
+    return 0;
+  }
+
+  // the last launch: slots [p0, p0 + n) of the partial rows summed into dst[0 .. n), or with
+  // adam into grad[p0 ..] and the TF-Adam update in the same kernel; fused: every other slot
+  // from the fused step kernel's rows (adam->fused)
+  int reduce(int p0, int n, float* dst) const {
+    hipLaunchKernelGGL(kw_grad_reduce, dim3(n), dim3(64), 0, st, part, w.segs, p0, o.NP, dst);
+    HIP_TRY(kmark("kw_grad_reduce", st));
+    return 0;
+  }
+  int tail(int p0, int n, float* grad, const WideAdam* adam, bool fused) const {
+    if (!adam) return reduce(p0, n, grad + p0);
+    hdg_state* S = adam->state;
+    const FusedRows fr = fused ? adam->fused : FusedRows{};
+    const int nfb = fused ? (fr.f_np + HDG_TRAILER + 15) / 16 : 0, nsb = (n + NW - 1) / NW;
+    hipLaunchKernelGGL(kw_reduce_adam, dim3(nfb + nsb), dim3(NT), 0, st, part, w.segs, o.NP, p0,
+                       p0 + n, nfb, fr, grad, S->params, S->adam_m, S->adam_v, S->beta_pow, D,
+                       adam->lr, adam->inv_pairs, adam->stats);
+    HIP_TRY(kmark("kw_reduce_adam", st));
+    return 0;
+  }
+};
 
 }  // namespace
 
 size_t wide_workspace_bytes(const hdg_shape* s) { return wide_layout(s).total * sizeof(float); }
 
 // ---- model_4 on the fused path (hdgnn.hip): the entity-edge stage on this path's kernels
-// around the fused step kernel, which runs the model_2-shaped rest of the step ----------
-float* wide_dn(const hdg_shape* s, void* workspace) {
-  return (float*)workspace + wide_layout(s).dn;
+// around the fused step kernel, which runs the model_2-shaped rest of the step; here
+// (ent, ee) = (false, true) ----------
+WideEE wide_ee_io(const hdg_shape* s, void* workspace) {
+  const WideWork w = wide_layout(s);
+  float* ws = (float*)workspace;
+  return WideEE{(const unsigned long long*)(ws + w.ncpart), ee_fwd_tiles(s->ne), ws + w.dn};
 }
-
-const unsigned long long* wide_ncpart(const hdg_shape* s, void* workspace) {
-  return (const unsigned long long*)((float*)workspace + wide_layout(s).ncpart);
-}
-int wide_ncpart_tiles(const hdg_shape* s) { return ee_fwd_tiles(s->ne); }
 
 int wide_ee_fwd(const hdg_shape* s, const hdg_batch* bt, const float* params, void* workspace,
                 hipStream_t st, const float* bpow) {
-  const int B = s->batch, Ne = s->ne, Nc = s->nc;
-  const Off o = param_offsets(s->variant);
-  const WideWork w = wide_layout(s);
-  float* ws = (float*)workspace;
-  auto F = [&](size_t off) { return ws + off; };
-  const uint32_t* prep = (const uint32_t*)bt->prep;
-  const uint32_t* aT = prep + (size_t)B * gen_prep(Ne, Nc).words;
-  const int te = (Ne + TN - 1) / TN;
+  const WideCtx c(s, bt, params, workspace, st);
   if (int rc = set_wide_attrs()) return rc;
-  const NodeFwdOut no{F(w.Eb), F(w.hE), F(w.ov), F(w.xp), F(w.Rn), F(w.Cn), F(w.rho), F(w.gmm)};
-  if (ent_fwd_halves((long long)te * B) == 2)
-    hipLaunchKernelGGL(kw_ent_fwd<2>, dim3(te + 1, B, 1), dim3(NTP), sort_lds_bytes(Ne), st,
-                       bt->x, bt->abits, aT, prep, params, o, Ne, Nc, 0, F(w.P), F(w.R1),
-                       F(w.C1), ws + w.D, bpow, no);
-  else
-    hipLaunchKernelGGL(kw_ent_fwd<1>, dim3(te + 1, B, 1), dim3(NT), sort_lds_bytes(Ne), st,
-                       bt->x, bt->abits, aT, prep, params, o, Ne, Nc, 0, F(w.P), F(w.R1),
-                       F(w.C1), ws + w.D, bpow, no);
-  WTRY(kmark("kw_ent_fwd", st));
-  unsigned long long* ncpart = (unsigned long long*)F(w.ncpart);
-  return launch_ee_fwd(s, bt, params, ws + w.D, F(w.rho), F(w.gmm), ncpart, st);
+  if (int rc = c.ent_fwd(false, true, bpow)) return rc;
+  return c.ee_fwd();
 }
 
 int wide_ee_bwd(const hdg_shape* s, const hdg_batch* bt, const float* params, void* workspace,
                 float* grad, hipStream_t st, const WideAdam* adam) {
-  const int B = s->batch, Ne = s->ne, Nc = s->nc;
-  const Off o = param_offsets(s->variant);
-  const WideWork w = wide_layout(s);
-  float* ws = (float*)workspace;
-  auto F = [&](size_t off) { return ws + off; };
-  const uint32_t* prep = (const uint32_t*)bt->prep;
-  const uint32_t* aT = prep + (size_t)B * gen_prep(Ne, Nc).words;
-  const int te = (Ne + TN - 1) / TN;
-  float* part = ws;
+  const WideCtx c(s, bt, params, workspace, st);
   if (int rc = set_wide_attrs()) return rc;
-  const int snake = ee_snake(s);
-  hipLaunchKernelGGL(kw_ee_clsb, dim3(ee_bwd_tiles(Ne), B, 1), dim3(NT), ee_clsb_lds(Ne), st, aT,
-                     bt->hid, bt->nlen, ws + w.D, Ne, Nc, snake, prep + ee_order_off(s), F(w.rho),
-                     F(w.gmm), F(w.dn), F(w.drho), F(w.dgam), part, w.segs);
-  WTRY(kmark("kw_ee_clsb", st));
-  hipLaunchKernelGGL(kw_ee_nodeb, dim3(te, B), dim3(NT), 0, st, params, o, ws + w.D, Ne,
-                     ee_bwd_tiles(Ne), bt->nlen, F(w.R1), F(w.C1), F(w.Rn), F(w.Cn), F(w.drho),
-                     F(w.dgam), F(w.phi), F(w.psi), part, w.segs);
-  WTRY(kmark("kw_ee_nodeb", st));
-  hipLaunchKernelGGL(kw_scan, dim3(H, B, 1), dim3(NT), 0, st, prep, params, o, Ne, Nc, 1,
-                     nullptr, F(w.psi), (double*)F(w.tab));
-  WTRY(kmark("kw_scan", st));
-  if (first_bwd_halves(te * B) == 2)
-    hipLaunchKernelGGL(kw_first_bwd<2>, dim3(te, B), dim3(NTP), sort_lds_bytes(Ne), st, bt->x,
-                       bt->abits, prep, params, o, Ne, Nc, 1, nullptr, F(w.phi), F(w.psi),
-                       (const double*)F(w.tab), part, w.segs);
-  else
-    hipLaunchKernelGGL(kw_first_bwd<1>, dim3(te, B), dim3(NT), sort_lds_bytes(Ne), st, bt->x,
-                       bt->abits, prep, params, o, Ne, Nc, 1, nullptr, F(w.phi), F(w.psi),
-                       (const double*)F(w.tab), part, w.segs);
-  WTRY(kmark("kw_first_bwd", st));
+  if (int rc = c.ee_bwd()) return rc;
+  if (int rc = c.first_bwd(false, true)) return rc;
   // the entity-edge parameters [EE_W11, EC_B2 + 2): one contiguous block of the flat vector
-  const int p0 = o.EE_W11, n = o.EC_B2 + 2 - o.EE_W11;
-  if (adam) {
-    hdg_state* S = adam->state;
-    const FusedRows& fr = adam->fused;   // the step kernel's rows: every other slot
-    const int nfb = (fr.f_np + HDG_TRAILER + 15) / 16, nsb = (n + NW - 1) / NW;
-    hipLaunchKernelGGL(kw_reduce_adam, dim3(nfb + nsb), dim3(NT), 0, st, part, w.segs, o.NP,
-                       p0, p0 + n, nfb, fr, grad, S->params, S->adam_m, S->adam_v, S->beta_pow,
-                       ws + w.D, adam->lr, adam->inv_pairs, adam->stats);
-  } else {
-    hipLaunchKernelGGL(kw_grad_reduce, dim3(n), dim3(64), 0, st, part, w.segs, p0, o.NP,
-                       grad + p0);
-  }
-  WTRY(kmark(adam ? "kw_reduce_adam" : "kw_grad_reduce", st));
-  return 0;
+  return c.tail(c.o.EE_W11, c.o.EC_B2 + 2 - c.o.EE_W11, grad, adam, true);
 }
 
 void wide_prep_counts_layout(const hdg_shape* s, int64_t* stride, int64_t* ks, int64_t* kt,
@@ -4717,33 +4873,37 @@ size_t wide_prep_bytes(const hdg_shape* s) {
 
 int wide_prepare(const hdg_shape* s, const hdg_batch* bt, hipStream_t st) {
   const GenPrep GP = gen_prep(s->ne, s->nc);
-  WTRY(launch_prep_maps(s, bt, GP.words, GP.ks, GP.kt, GP.ncst, st));
-  hipLaunchKernelGGL(kw_prep_sort, dim3(s->batch), dim3(1024), (size_t)2 * s->ne * 4, st, bt->x,
-                     (uint32_t*)bt->prep, s->ne, s->nc);
-  WTRY(kmark("kw_prep_sort", st));
-  uint32_t* aT = (uint32_t*)bt->prep + (size_t)s->batch * GP.words;
-  uint32_t* yT = aT + (size_t)s->batch * s->ne * ((s->ne + 31) / 32);
-  hipLaunchKernelGGL(kw_prep_T, dim3(8, s->batch), dim3(NT), 0, st, bt->abits, aT, s->ne);
-  WTRY(kmark("kw_prep_T", st));
-  hipLaunchKernelGGL(kw_prep_T, dim3(4, s->batch), dim3(NT), 0, st, bt->ybits, yT, s->nc);
-  WTRY(kmark("kw_prep_T", st));
-  if (has_ent(s->variant)) {   // the entity walks' neighbour lists
-    hipLaunchKernelGGL(kw_prep_lists, dim3((s->ne + NW - 1) / NW, s->batch, 2), dim3(NT), 0, st,
-                       bt->abits, aT, (uint32_t*)bt->prep, s->ne,
-                       list_layout(s->batch, s->ne, s->nc));
-    WTRY(kmark("kw_prep_lists", st));
-  }
-  if (hunk_lists(s)) {         // the sorted hunk passes' label lists
-    hipLaunchKernelGGL(kw_prep_lists, dim3((s->nc + NW - 1) / NW, s->batch, 2), dim3(NT), 0, st,
-                       bt->ybits, yT, (uint32_t*)bt->prep, s->nc,
-                       ylist_layout(s->batch, s->ne, s->nc, has_ent(s->variant)));
-    WTRY(kmark("kw_prep_lists", st));
-  }
+  const int B = s->batch;
+  uint32_t* prep = (uint32_t*)bt->prep;
+  HIP_TRY(launch_prep_maps(s, bt, GP.words, GP.ks, GP.kt, GP.ncst, st));
+  hipLaunchKernelGGL(kw_prep_sort, dim3(B), dim3(1024), (size_t)2 * s->ne * 4, st, bt->x, prep,
+                     s->ne, s->nc);
+  HIP_TRY(kmark("kw_prep_sort", st));
+  // the transposed bits of an n x n matrix per commit, then its rows' / columns' id lists
+  auto transpose = [&](int gx, const uint32_t* bits, uint32_t* T, int n) -> int {
+    hipLaunchKernelGGL(kw_prep_T, dim3(gx, B), dim3(NT), 0, st, bits, T, n);
+    HIP_TRY(kmark("kw_prep_T", st));
+    return 0;
+  };
+  auto lists = [&](const uint32_t* bits, const uint32_t* T, int n, const ListLayout& LL) -> int {
+    hipLaunchKernelGGL(kw_prep_lists, dim3((n + NW - 1) / NW, B, 2), dim3(NT), 0, st, bits, T,
+                       prep, n, LL);
+    HIP_TRY(kmark("kw_prep_lists", st));
+    return 0;
+  };
+  uint32_t* aT = prep + (size_t)B * GP.words;
+  uint32_t* yT = aT + (size_t)B * s->ne * ((s->ne + 31) / 32);
+  if (int rc = transpose(8, bt->abits, aT, s->ne)) return rc;
+  if (int rc = transpose(4, bt->ybits, yT, s->nc)) return rc;
+  if (has_ent(s->variant))     // the entity walks' neighbour lists
+    if (int rc = lists(bt->abits, aT, s->ne, list_layout(B, s->ne, s->nc))) return rc;
+  if (hunk_lists(s))           // the sorted hunk passes' label lists
+    if (int rc = lists(bt->ybits, yT, s->nc, ylist_layout(B, s->ne, s->nc, has_ent(s->variant))))
+      return rc;
   if (has_ee(s->variant) && ee_snake(s) > 0) {   // the entity-edge kernels' dispatch orders
-    hipLaunchKernelGGL(kw_prep_order, dim3(1), dim3(1024),
-                       (size_t)ee_fwd_tiles(s->ne) * s->batch * 4, st, bt->nlen, s->batch, s->ne,
-                       (uint32_t*)bt->prep + ee_order_off(s));
-    WTRY(kmark("kw_prep_order", st));
+    hipLaunchKernelGGL(kw_prep_order, dim3(1), dim3(1024), (size_t)ee_fwd_tiles(s->ne) * B * 4, st,
+                       bt->nlen, B, s->ne, prep + ee_order_off(s));
+    HIP_TRY(kmark("kw_prep_order", st));
   }
   return 0;
 }
@@ -4819,229 +4979,52 @@ hipError_t launch_ehr(const float* G, const float* Hh, size_t cs, int B, int Nc,
   const Off o = param_offsets(variant);
   hipLaunchKernelGGL(kw_ehr, dim3(1), dim3(1024), 0, st, G, Hh, cs, B, Nc, params, o.H1_W2,
                      o.H1_B2, out);
-  return hipGetLastError();
+  return kmark("kw_ehr", st);
 }
 
 int wide_run(const hdg_shape* s, const hdg_batch* bt, const float* params, float* grad,
              hdg_outputs* out, float* ce_sum, void* workspace, bool train, hipStream_t st,
              const WideAdam* adam) {
-  const int B = s->batch, Ne = s->ne, Nc = s->nc, v = s->variant;
-  const Off o = param_offsets(v);
-  const WideWork w = wide_layout(s);
-  float* ws = (float*)workspace;
-  const uint32_t* prep = (const uint32_t*)bt->prep;
-  const uint32_t* aT = prep + (size_t)B * gen_prep(Ne, Nc).words;
-  const uint32_t* yT = aT + (size_t)B * Ne * ((Ne + 31) / 32);
-  const int te = (Ne + TN - 1) / TN, tc = (Nc + TN - 1) / TN;
-  const bool ent = has_ent(v), ee = has_ee(v);
-  const int bg = s->batch_global > 0 ? s->batch_global : B;
-  const float ce_scale = 10.f / ((float)bg * (float)(Nc * (Nc - 1)));
-  float* D = ws + w.D;
-  float* part = ws;   // segment offsets are absolute
-  auto F = [&](size_t off) { return ws + off; };
-
-  const size_t tlds = sort_lds_bytes(Ne);
-  if (int rc = set_wide_attrs()) return rc;
+  const WideCtx c(s, bt, params, workspace, st);
+  const bool ent = has_ent(c.v), ee = has_ee(c.v);
+  const float ce_scale = 10.f / pair_count(s);
   const float* bpow = train && adam ? adam->state->beta_pow : nullptr;
-  if (!(ent || ee)) {
-    hipLaunchKernelGGL(kw_derive, dim3(1), dim3(NT), 0, st, params, o, Nc, D, bpow);
-    WTRY(kmark("kw_derive", st));
-  }
+  if (int rc = set_wide_attrs()) return rc;
   // ---- entity side ----
-  if (ent || ee) {   // + kw_derive's work in one more block column, node_fwd_tile per tile
-    const NodeFwdOut no{F(w.Eb), F(w.hE), F(w.ov), F(w.xp), F(w.Rn), F(w.Cn), F(w.rho),
-                        F(w.gmm)};
-    const int ez = (ent && ee) ? 2 : 1;
-    if (ent_fwd_halves((long long)te * B * ez) == 2)
-      hipLaunchKernelGGL(kw_ent_fwd<2>, dim3(te + 1, B, ez), dim3(NTP), tlds, st, bt->x,
-                         bt->abits, aT, prep, params, o, Ne, Nc, ent ? 1 : 0, F(w.P), F(w.R1),
-                         F(w.C1), D, bpow, no);
-    else
-      hipLaunchKernelGGL(kw_ent_fwd<1>, dim3(te + 1, B, ez), dim3(NT), tlds, st, bt->x,
-                         bt->abits, aT, prep, params, o, Ne, Nc, ent ? 1 : 0, F(w.P), F(w.R1),
-                         F(w.C1), D, bpow, no);
-    WTRY(kmark("kw_ent_fwd", st));
-  }
-  unsigned long long* ncpart = ee ? (unsigned long long*)F(w.ncpart) : nullptr;
-  if (ee) {
-    if (int rc = launch_ee_fwd(s, bt, params, D, F(w.rho), F(w.gmm), ncpart, st)) return rc;
-  }
+  if (int rc = (ent || ee) ? c.ent_fwd(ent, ee, bpow) : c.derive(bpow)) return rc;
+  if (ee)
+    if (int rc = c.ee_fwd()) return rc;
   // ---- hunk side ----
-  hipLaunchKernelGGL(kw_cross_fwd, dim3((Nc + NW - 1) / NW, B), dim3(NT), 0, st, prep,
-                     ent ? F(w.xp) : bt->x, params, o, Ne, Nc, ncpart, ee_fwd_tiles(Ne), F(w.nvec), F(w.alpha),
-                     F(w.beta));
-  WTRY(kmark("kw_cross_fwd", st));
-  const bool hs = hunk_sorted(s), ht = hunk_tiled(s);
-  const ListLayout YL = ylist_layout(B, Ne, Nc, ent);
-  const HTileSums hts{F(w.htr), F(w.htc), F(w.hty), (Nc + hunk_tile_cols() - 1) / hunk_tile_cols(),
-                      (Nc + hunk_tile_rows() - 1) / hunk_tile_rows()};
-  if (hs) {
-    const dim3 gw(H, B, 2);
-#define HDG_SORT(E_)                                                                            \
-  hipLaunchKernelGGL(kw_hunk_sort<E_>, gw, dim3(NT), 0, st, F(w.alpha), F(w.beta), Nc, F(w.hsv), \
-                     (int*)F(w.hsp), (double*)F(w.hsx))
-    switch (hsort_e(Nc)) {
-      case 1: HDG_SORT(1); break;
-      case 2: HDG_SORT(2); break;
-      case 4: HDG_SORT(4); break;
-      default: HDG_SORT(8); break;
-    }
-#undef HDG_SORT
-    WTRY(kmark("kw_hunk_sort", st));
-    if (hs_all_shape(s)) {
-      hipLaunchKernelGGL(kw_hunk_fwd_s, dim3((Nc + HSN - 1) / HSN, B, 2), dim3(HS_NT),
-                         hs_shape_lds_bytes(s, 1), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
-                         F(w.hsv), (const double*)F(w.hsx), prep, YL, F(w.G), F(w.Hh),
-                         F(w.sig), F(w.tau));
-      WTRY(kmark("kw_hunk_fwd_s", st));
-    } else {
-      hipLaunchKernelGGL(kw_hunk_fwd_g, dim3(4 * hs_tiles(Nc), B, 2), dim3(NT),
-                         hs_shape_lds_bytes(s, 1), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
-                         F(w.hsv), (const double*)F(w.hsx), prep, YL, F(w.G), F(w.Hh));
-      WTRY(kmark("kw_hunk_fwd_g", st));
-      hipLaunchKernelGGL(kw_hunk_sig, dim3(tc, B, 2), dim3(NT), 0, st, D, Nc, F(w.G), F(w.Hh),
-                         F(w.sig), F(w.tau));
-      WTRY(kmark("kw_hunk_sig", st));
-    }
-  } else if (ht) {
-    HTileArgs ha{Nc, F(w.alpha), F(w.beta), nullptr, nullptr, nullptr, D + D_DLT, bt->ybits,
-                 F(w.htr), F(w.htc), F(w.hty)};
-    WTRY(launch_hunk_tile(0, ha, B, st));
-    hipLaunchKernelGGL(kw_hunk_fin0, dim3(tc, B, 2), dim3(NTP), 0, st, hts, D, Nc, F(w.alpha),
-                       F(w.beta), F(w.G), F(w.Hh), F(w.sig), F(w.tau));
-    WTRY(kmark("kw_hunk_fin0", st));
-  } else {
-    hipLaunchKernelGGL(kw_hunk_fwd, dim3(tc, B, 2), dim3(NTP), 0, st, bt->ybits, yT, D, Nc,
-                       F(w.alpha), F(w.beta), F(w.G), F(w.Hh), F(w.sig), F(w.tau));
-    WTRY(kmark("kw_hunk_fwd", st));
-  }
-  float* probs = out ? out->probs : nullptr;
-  float* logits = out ? out->logits : nullptr;
+  if (int rc = c.cross_fwd(ent, ee)) return rc;
+  if (int rc = c.hunk_fwd()) return rc;
   if (!train) {
-    hipLaunchKernelGGL(kw_hunk_cls<false>, dim3(tc, B, CLS_SPLIT), dim3(NTP), 0, st, yT, params,
-                       o, D,
-                       Nc, F(w.sig), F(w.tau), probs, logits, F(w.gam), ce_scale, part, w.segs, 0);
-    WTRY(kmark("kw_hunk_cls", st));
-    if (ce_sum) {
-      hipLaunchKernelGGL(kw_grad_reduce, dim3(1), dim3(64), 0, st, part, w.segs, o.NP, o.NP,
-                         ce_sum);
-      WTRY(kmark("kw_grad_reduce", st));
-    }
+    if (int rc = c.hunk_cls<false>(out, ce_scale, 0)) return rc;
+    if (ce_sum)
+      if (int rc = c.reduce(c.o.NP, 1, ce_sum)) return rc;
     if (out && out->ehr) {
-      WTRY(launch_ehr(F(w.G), F(w.Hh), (size_t)Nc * H, B, Nc, params, v, out->ehr, st));
+      HIP_TRY(launch_ehr(c.F(c.w.G), c.F(c.w.Hh), (size_t)c.Nc * H, c.B, c.Nc, params, c.v,
+                         out->ehr, st));
     }
     return 0;
   }
   // the two-pass classifier backward rebuilds gamma from the probabilities when the step
   // writes them (a training sess.run fetches C_edge_output2): 4 B per pair not stored
-  const float* gprobs = (!ht && HDG_GAM_FROM_PROBS) ? probs : nullptr;
-  hipLaunchKernelGGL(kw_hunk_cls<true>, dim3(tc, B, CLS_SPLIT), dim3(NTP), 0, st, yT, params,
-                     o, D, Nc,
-                     F(w.sig), F(w.tau), probs, logits, F(w.gam), ce_scale, part, w.segs,
-                     gprobs ? 0 : 1);
-  WTRY(kmark("kw_hunk_cls", st));
-  if (ht) {
-    HTileArgs ha{Nc, F(w.sig), F(w.tau), nullptr, nullptr, F(w.gam), D + D_EPS, bt->ybits,
-                 F(w.htr), F(w.htc), F(w.hty)};
-    WTRY(launch_hunk_tile(2, ha, B, st));
-    hipLaunchKernelGGL(kw_hunk_fin2, dim3(tc, B, 2), dim3(NTP), 0, st, hts, params, o, D, Nc,
-                       F(w.G), F(w.Hh), F(w.Dsig), F(w.Dtau), F(w.dG), F(w.dH), part, w.segs);
-    WTRY(kmark("kw_hunk_fin2", st));
-  } else {
-    hipLaunchKernelGGL(kw_hunk_clsb, dim3(tc, B, 2), dim3(NTP), 0, st, bt->ybits, yT, params, o,
-                       D, Nc, F(w.sig), F(w.tau), F(w.gam), F(w.G), F(w.Hh), F(w.Dsig),
-                       F(w.Dtau), F(w.dG), F(w.dH), part, w.segs, gprobs, ce_scale);
-    WTRY(kmark("kw_hunk_clsb", st));
-  }
-  if (hs) {
-    const dim3 gw(H, B, 2);
-#define HDG_WSUM(E_)                                                                        \
-  hipLaunchKernelGGL(kw_hunk_wsum<E_>, gw, dim3(NT), 0, st, (const int*)F(w.hsp), F(w.dG), \
-                     F(w.dH), Nc, (double*)F(w.hsw))
-    switch (hsort_e(Nc)) {
-      case 1: HDG_WSUM(1); break;
-      case 2: HDG_WSUM(2); break;
-      case 4: HDG_WSUM(4); break;
-      default: HDG_WSUM(8); break;
-    }
-#undef HDG_WSUM
-    WTRY(kmark("kw_hunk_wsum", st));
-    if (hs_all_shape(s)) {
-      hipLaunchKernelGGL(kw_hunk_mlpb_s, dim3((Nc + HSN - 1) / HSN, B, 2), dim3(HS_NT),
-                         hs_shape_lds_bytes(s, 2), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
-                         F(w.dG), F(w.dH), F(w.nvec), F(w.hsv), (const double*)F(w.hsw), prep,
-                         YL, F(w.Dal), F(w.Dbe), part, w.segs);
-      WTRY(kmark("kw_hunk_mlpb_s", st));
-    } else {
-      hipLaunchKernelGGL(kw_hunk_mlpb_g, dim3(4 * hs_tiles(Nc), B, 2), dim3(NT),
-                         hs_shape_lds_bytes(s, 2), st, bt->ybits, yT, D, Nc, F(w.alpha), F(w.beta),
-                         F(w.dG), F(w.dH), F(w.nvec), F(w.hsv), (const double*)F(w.hsw), prep,
-                         YL, F(w.Dal), F(w.Dbe), part, w.segs);
-      WTRY(kmark("kw_hunk_mlpb_g", st));
-    }
-  } else if (ht) {
-    HTileArgs ha{Nc, F(w.alpha), F(w.beta), F(w.dG), F(w.dH), nullptr, D + D_DLT, bt->ybits,
-                 F(w.htr), F(w.htc), F(w.hty)};
-    WTRY(launch_hunk_tile(1, ha, B, st));
-    hipLaunchKernelGGL(kw_hunk_fin1, dim3(tc, B, 2), dim3(NTP), 0, st, hts, D, Nc, F(w.alpha),
-                       F(w.beta), F(w.dG), F(w.dH), F(w.nvec), F(w.Dal), F(w.Dbe), part, w.segs);
-    WTRY(kmark("kw_hunk_fin1", st));
-  } else {
-    hipLaunchKernelGGL(kw_hunk_mlpb, dim3(tc, B, 2), dim3(NTP), 0, st, bt->ybits, yT, D, Nc,
-                       F(w.alpha), F(w.beta), F(w.dG), F(w.dH), F(w.nvec), F(w.Dal), F(w.Dbe),
-                       part, w.segs);
-    WTRY(kmark("kw_hunk_mlpb", st));
-  }
-  if (ee) {   // kw_ee_clsb reads dn; with the entity stage alone kw_node_bwd forms it itself
-    hipLaunchKernelGGL(kw_dn, dim3(tc, B), dim3(NT), 0, st, params, o, Nc, F(w.Dal), F(w.Dbe),
-                       F(w.dn));
-    WTRY(kmark("kw_dn", st));
-  }
-  if (ent) {
-    hipLaunchKernelGGL(kw_node_bwd, dim3(te, B), dim3(NT), 0, st, prep, bt->x, params, o, Ne, Nc,
-                       ee ? F(w.dn) : nullptr, F(w.ov), F(w.P), F(w.Eb), F(w.hE), F(w.rhoE), part,
-                       w.segs, F(w.Dal), F(w.Dbe));
-    WTRY(kmark("kw_node_bwd", st));
-  }
-  if (ee) {
-    const int snake = ee_snake(s);
-    hipLaunchKernelGGL(kw_ee_clsb, dim3(ee_bwd_tiles(Ne), B, 1), dim3(NT), ee_clsb_lds(Ne), st,
-                       aT, bt->hid, bt->nlen, D, Ne, Nc, snake, prep + ee_order_off(s), F(w.rho),
-                       F(w.gmm), F(w.dn), F(w.drho), F(w.dgam), part, w.segs);
-    WTRY(kmark("kw_ee_clsb", st));
-    hipLaunchKernelGGL(kw_ee_nodeb, dim3(te, B), dim3(NT), 0, st, params, o, D, Ne,
-                       ee_bwd_tiles(Ne), bt->nlen, F(w.R1), F(w.C1), F(w.Rn), F(w.Cn), F(w.drho),
-                       F(w.dgam), F(w.phi), F(w.psi), part, w.segs);
-    WTRY(kmark("kw_ee_nodeb", st));
-  }
-  if (ent || ee) {   // the first-layer backward of both stages: one scan, one launch
-    const int mode0 = ent ? 0 : 1, stages = (ent && ee) ? 2 : 1;
-    hipLaunchKernelGGL(kw_scan, dim3(H, B, stages), dim3(NT), 0, st, prep, params, o, Ne, Nc,
-                       mode0, F(w.rhoE), F(w.psi), (double*)F(w.tab));
-    WTRY(kmark("kw_scan", st));
-    if (first_bwd_halves(te * B * stages) == 2)
-      hipLaunchKernelGGL(kw_first_bwd<2>, dim3(te, B, stages), dim3(NTP), tlds, st, bt->x,
-                         bt->abits, prep, params, o, Ne, Nc, mode0, F(w.rhoE), F(w.phi),
-                         F(w.psi), (const double*)F(w.tab), part, w.segs);
-    else
-      hipLaunchKernelGGL(kw_first_bwd<1>, dim3(te, B, stages), dim3(NT), tlds, st, bt->x,
-                         bt->abits, prep, params, o, Ne, Nc, mode0, F(w.rhoE), F(w.phi),
-                         F(w.psi), (const double*)F(w.tab), part, w.segs);
-    WTRY(kmark("kw_first_bwd", st));
-  }
-  if (adam) {
-    hdg_state* S = adam->state;
-    const int nsb = (o.NP + HDG_TRAILER + NW - 1) / NW;
-    hipLaunchKernelGGL(kw_reduce_adam, dim3(nsb), dim3(NT), 0, st, part, w.segs, o.NP, 0,
-                       o.NP + HDG_TRAILER, 0, FusedRows{}, grad, S->params, S->adam_m,
-                       S->adam_v, S->beta_pow, D, adam->lr, adam->inv_pairs, adam->stats);
-  } else {
-    hipLaunchKernelGGL(kw_grad_reduce, dim3(o.NP + HDG_TRAILER), dim3(64), 0, st, part, w.segs,
-                       0, o.NP, grad);
-  }
-  WTRY(kmark(adam ? "kw_reduce_adam" : "kw_grad_reduce", st));
-  return 0;
+  const float* gprobs = (c.hf != HF_TILED && HDG_GAM_FROM_PROBS && out) ? out->probs : nullptr;
+  if (int rc = c.hunk_cls<true>(out, ce_scale, gprobs ? 0 : 1)) return rc;
+  if (int rc = c.hunk_clsb(gprobs, ce_scale)) return rc;
+  if (int rc = c.hunk_mlpb()) return rc;
+  // ---- entity side, backward ----
+  if (ee)
+    if (int rc = c.dn()) return rc;
+  if (ent)
+    if (int rc = c.node_bwd(ee)) return rc;
+  if (ee)
+    if (int rc = c.ee_bwd()) return rc;
+  if (ent || ee)
+    if (int rc = c.first_bwd(ent, ee)) return rc;
+  return c.tail(0, c.o.NP + HDG_TRAILER, grad, adam, false);
 }
+
 
 }  // namespace hdg
 
