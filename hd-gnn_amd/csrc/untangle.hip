@@ -22,78 +22,21 @@
 //               label graph from the set bits of ybits, counts the pairs of the two
 //               labelings and writes groups, tgroups and the ut row.
 //
-// Union-find, lock-free with min-root hooking.  Invariant: parent[i] <= i, and parent[i]
-// is always a node of i's own component.  find walks parent to a root (parent[r] == r) with
-// atomic LDS loads; union finds both roots, returns when they are equal, else tries
-// atomicCAS(&parent[hi], hi, lo) with hi > lo and on failure goes on from the value it read.
-// A CAS fails only because another thread lowered that word, and words only ever decrease
-// towards 0: the pair (hi, lo) a union holds strictly decreases with every failure, so every
-// loop ends within 2 Nc steps and none waits for a particular thread.  Path halving stores
-// parent[x] <- a value read as x's grandparent: a smaller node of the same tree, written only
-// to non-roots (a non-root never becomes a root again, and the CAS only ever changes roots).
+// The union-find (lock-free, min-root hooking), the labelling and the tile geometry are
+// unionfind.h's, shared with linkage.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hdgnn_internal.h"
+#include "unionfind.h"
 
 namespace {
 
 using hdg::fail;
 
-constexpr int UT_T = HDG_UT_TILE;            // tile side
-constexpr int UT_LD = UT_T + 1;              // padded LDS row stride (words)
-constexpr int UT_MAXN = 2048;                // nc limit of the ABI
-constexpr int UT_LINK_NT = 512;
-constexpr int UT_LINK_WAVES = UT_LINK_NT / 64;
-constexpr int UT_CLOSE_NT = 1024;
-constexpr int UT_CLOSE_WAVES = UT_CLOSE_NT / 64;
-constexpr int UT_PER = UT_MAXN / UT_CLOSE_NT;   // nodes per thread of the closing block
-
-static_assert(UT_T == 64, "the tile visit maps one wave to one tile row");
-
-__host__ __device__ inline int ut_blocks(const int nc) {
-  const int T = (nc + UT_T - 1) / UT_T;
-  const int tiles = T * (T + 1) / 2;
-  const int n = (tiles + HDG_UT_TILES_PER_BLOCK - 1) / HDG_UT_TILES_PER_BLOCK;
-  return n < HDG_UT_MAX_BLOCKS ? n : HDG_UT_MAX_BLOCKS;
-}
 // workspace, in 4-byte words per commit: nblk forests of nc words, then nblk {LINKS, NAN}
 __host__ __device__ inline size_t ut_commit_words(const int nc, const int nblk) {
   return (size_t)nblk * (size_t)(nc + 2);
-}
-
-__device__ __forceinline__ uint32_t ut_ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ uint32_t ut_find(uint32_t* parent, uint32_t x) {
-  uint32_t p = ut_ld(&parent[x]);
-  while (p != x) {
-    const uint32_t g = ut_ld(&parent[p]);
-    if (g != p) __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-__device__ __forceinline__ void ut_union(uint32_t* parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = ut_find(parent, a);
-    b = ut_find(parent, b);
-    if (a == b) return;
-    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-    const uint32_t old = atomicCAS(&parent[hi], hi, lo);
-    if (old == hi) return;
-    a = old;       // parent[hi] was lowered by someone else: old < hi, same component
-    b = lo;
-  }
-}
-
-__device__ __forceinline__ uint32_t ut_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_down((int)v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(UT_LINK_NT) void k_ut_link(const float* __restrict__ probs,
@@ -174,55 +117,6 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_ut_link(const float* __restrict_
   }
 }
 
-// par holds a forest over 0 .. nc-1 (all unions done, block synchronised).  Flattens it,
-// numbers the roots in ascending order (the dense id of a root = the roots below it: a
-// block-wide exclusive scan of the root flags) and writes every node's id to out.
-// Returns the number of components.  Whole block, uniform control flow.
-__device__ __forceinline__ uint32_t ut_label(uint32_t* par, uint32_t* rnk, uint32_t* out,
-                                             uint32_t* wsum, const int nc) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t r[UT_PER];
-#pragma unroll
-  for (int u = 0; u < UT_PER; ++u) {
-    const int i = tid + u * UT_CLOSE_NT;
-    r[u] = i < nc ? ut_find(par, (uint32_t)i) : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < UT_PER; ++u) {
-    const int i = tid + u * UT_CLOSE_NT;
-    if (i < nc) par[i] = r[u];
-  }
-  __syncthreads();
-  uint32_t base = 0;
-#pragma unroll
-  for (int u = 0; u < UT_PER; ++u) {
-    if (u * UT_CLOSE_NT >= nc) break;                       // uniform
-    const int i = tid + u * UT_CLOSE_NT;
-    const bool root = i < nc && r[u] == (uint32_t)i;
-    const unsigned long long m = __ballot(root);
-    const uint32_t pre = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = base, tot = 0;
-    for (int w = 0; w < UT_CLOSE_WAVES; ++w) {
-      const uint32_t v = wsum[w];
-      off += w < wave ? v : 0u;
-      tot += v;
-    }
-    if (i < nc) rnk[i] = off + pre;
-    base += tot;
-    __syncthreads();
-  }
-#pragma unroll
-  for (int u = 0; u < UT_PER; ++u) {
-    const int i = tid + u * UT_CLOSE_NT;
-    if (i < nc) out[i] = rnk[r[u]];
-  }
-  __syncthreads();
-  return base;
-}
-
 __global__ __launch_bounds__(UT_CLOSE_NT) void k_ut_close(const uint32_t* __restrict__ ws,
                                                           const uint32_t* __restrict__ ybits,
                                                           int32_t* __restrict__ groups,
@@ -256,19 +150,7 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_ut_close(const uint32_t* __rest
   // ---- true groups: the set bits of the commit's label rows ------------------------------
   for (int i = tid; i < nc; i += UT_CLOSE_NT) par[i] = (uint32_t)i;
   __syncthreads();
-  const int W = (nc + 31) >> 5, nwords = nc * W;
-  const uint32_t* yb = ybits + (size_t)b * nwords;
-  for (int w = tid; w < nwords; w += UT_CLOSE_NT) {
-    uint32_t bits = yb[w];
-    if (!bits) continue;
-    const int i = w / W, jb = (w - i * W) << 5;
-    while (bits) {
-      const int j = jb + __ffs((int)bits) - 1;
-      bits &= bits - 1;
-      if (j >= nc || j == i) continue;        // stray pad / diagonal bits: not relations
-      ut_union(par, (uint32_t)i, (uint32_t)j);
-    }
-  }
+  ut_unite_labels(par, ybits + (size_t)b * nc * ((nc + 31) >> 5), nc);
   __syncthreads();
   const uint32_t TG = ut_label(par, rnk, t, wsum, nc);
 
@@ -332,15 +214,6 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_ut_close(const uint32_t* __rest
     row[HDG_UT_LINKS] = links;
     row[HDG_UT_NAN] = nans;
   }
-}
-
-int ut_check_shape(const hdg_shape* s, const char* who) {
-  if (!s) return fail(HDG_EINVAL, "%s: shape is NULL", who);
-  if (s->batch < 1 || s->batch > 65535)
-    return fail(HDG_EINVAL, "%s: batch must be in [1, 65535] (got %d)", who, s->batch);
-  if (s->nc < 2 || s->nc > UT_MAXN)
-    return fail(HDG_EINVAL, "%s: nc must be in [2, 2048] (got %d)", who, s->nc);
-  return 0;
 }
 
 }  // namespace

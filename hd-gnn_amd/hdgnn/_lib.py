@@ -68,6 +68,9 @@ UT_GROUPS, UT_TGROUPS, UT_SS, UT_SD, UT_DS, UT_DD, UT_LINKS, UT_NAN = range(8)
 UT_RULE_MEAN, UT_RULE_ANY, UT_RULE_BOTH = 0, 1, 2
 UT_RULES = {"mean": UT_RULE_MEAN, "any": UT_RULE_ANY, "both": UT_RULE_BOTH}
 UT_TILE, UT_TILES_PER_BLOCK, UT_MAX_BLOCKS = 64, 4, 16
+# hdg_linkage's per-commit row (include/hdgnn.h): lk[B][LK_SLOTS] u64
+LK_SLOTS = 8
+LK_MERGES, LK_TGROUPS, LK_ST, LK_NAN, LK_PAIRS = range(5)
 
 
 def untangle_blocks(nc):
@@ -92,7 +95,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_bundle_write", "hdg_ckpt_writer_create", "hdg_ckpt_writer_submit",
            "hdg_ckpt_writer_flush", "hdg_ckpt_writer_poll", "hdg_ckpt_writer_destroy", "hdg_memcpy_async",
            "hdg_event_create", "hdg_event_record", "hdg_event_synchronize", "hdg_event_destroy",
-           "hdg_eval", "hdg_untangle_workspace_bytes", "hdg_untangle"]
+           "hdg_eval", "hdg_untangle_workspace_bytes", "hdg_untangle",
+           "hdg_linkage_workspace_bytes", "hdg_linkage"]
 
 _lib = None
 
@@ -135,6 +139,9 @@ def load(path=None):
     lib.hdg_untangle_workspace_bytes.argtypes = [P(Shape)]
     lib.hdg_untangle_workspace_bytes.restype = ctypes.c_size_t
     lib.hdg_untangle.argtypes = [P(Shape), P(Batch), vp, f32, i32, vp, vp, vp, vp, vp]
+    lib.hdg_linkage_workspace_bytes.argtypes = [P(Shape)]
+    lib.hdg_linkage_workspace_bytes.restype = ctypes.c_size_t
+    lib.hdg_linkage.argtypes = [P(Shape), P(Batch), vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

@@ -419,3 +419,46 @@ class Engine:
                                          ctypes.c_void_p(self._ut_workspace.data_ptr()),
                                          self._stream()))
         return groups, ut
+
+    def linkage(self, dbatch, probs=None, rule="mean"):
+        """hdg_linkage: the single-linkage merge tree of every commit's pair weights under
+        `rule` ("mean" | "any" | "both"; include/hdgnn.h) -- every partition untangle() can
+        give, at every threshold at once -- and the pair counts of each cut against the
+        batch's true groups.  `probs` as untangle()'s.  -> (merges int32 [B][nc-1][2], levels
+        float32 [B][nc-1], curve int32 [B][nc-1][2], tgroups int32 [B][nc], lk int64
+        [B][LK_SLOTS]) as fresh device tensors (hdgnn.metrics.best_threshold turns levels,
+        curve and lk into the best threshold).  Enqueued on the current stream; nothing is
+        copied to the host.  The workspace is allocated on the first call and kept."""
+        self._check(dbatch)
+        probs = self.probs if probs is None else probs
+        if (probs.device != self.device or probs.dtype != torch.float32
+                or not probs.is_contiguous()
+                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
+            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
+                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        if rule not in _lib.UT_RULES:
+            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        if getattr(self, "_lk_workspace", None) is None:
+            nbytes = self.lib.hdg_linkage_workspace_bytes(ctypes.byref(self.shape))
+            if nbytes == 0:
+                raise RuntimeError(self.lib.hdg_last_error().decode())
+            self._lk_workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        n1 = self.nc - 1
+        merges = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
+        levels = torch.empty(self.batch, n1, dtype=torch.float32, device=self.device)
+        # u32 / u64 counts, every value < 2^31 (at most nc (nc-1) / 2 pairs): int32 and int64
+        # read them as they are
+        curve = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
+        tgroups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
+        lk = torch.empty(self.batch, _lib.LK_SLOTS, dtype=torch.int64, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_linkage(ctypes.byref(self.shape), ctypes.byref(b),
+                                        ctypes.c_void_p(probs.data_ptr()), _lib.UT_RULES[rule],
+                                        ctypes.c_void_p(merges.data_ptr()),
+                                        ctypes.c_void_p(levels.data_ptr()),
+                                        ctypes.c_void_p(curve.data_ptr()),
+                                        ctypes.c_void_p(tgroups.data_ptr()),
+                                        ctypes.c_void_p(lk.data_ptr()),
+                                        ctypes.c_void_p(self._lk_workspace.data_ptr()),
+                                        self._stream()))
+        return merges, levels, curve, tgroups, lk

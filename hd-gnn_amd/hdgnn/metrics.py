@@ -272,3 +272,185 @@ def scores_from_untangle(ut):
                                 else float("nan"))
     out["nan_pairs"] = int(ut[:, UT_NAN].sum())
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# Linkage: every partition a threshold can give, at once -- the single-linkage merge tree of
+# a commit's pair weights and the pair counts of each of its cuts, as hdg_linkage computes
+# them on the device (include/hdgnn.h, HDG_LK_*), its host implementation, and the exactly
+# optimal threshold of a set of commits that follows from them.
+# ---------------------------------------------------------------------------------------
+LK_SLOTS = 8
+LK_MERGES, LK_TGROUPS, LK_ST, LK_NAN, LK_PAIRS = range(5)
+
+
+def _nc_of(R):
+    nc = int(round((1.0 + np.sqrt(1.0 + 4.0 * R)) / 2.0))
+    if nc < 2 or nc * (nc - 1) != R:
+        raise ValueError("R = %d is not Nc (Nc - 1)" % R)
+    return nc
+
+
+def linkage(label_onehot, probs, rule="mean"):
+    """(B, 2, R) one-hot labels and probabilities, R = Nc (Nc - 1) -> (merges int32
+    (B, Nc-1, 2), levels float32 (B, Nc-1), curve int64 (B, Nc-1, 2), tgroups int32 (B, Nc),
+    lk int64 (B, LK_SLOTS)): the host implementation of hdg_linkage, definitions as in
+    include/hdgnn.h.  Plain Kruskal: every edge {p, q}, p < q, with its weight under the rule
+    (mean: s_pq + s_qp in float32, any: the larger, both: the smaller; no edge when the
+    weight is NaN; -0 counts as +0) sorted by (weight descending, p, q), then one sequential
+    pass of unions.  The curve comes from the clusters' true-group histograms: a merge of A
+    and B adds |A| |B| same-predicted pairs, sum_g A_g B_g of them in one true group."""
+    from .data import pair_index
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    label = np.asarray(label_onehot)
+    probs = np.asarray(probs, np.float32)
+    B, R = probs.shape[0], probs.shape[2]
+    nc = _nc_of(R)
+    I, J = pair_index(nc)
+    iu, ju = np.triu_indices(nc, 1)
+    merges = np.full((B, nc - 1, 2), -1, np.int32)
+    levels = np.full((B, nc - 1), np.nan, np.float32)
+    curve = np.zeros((B, nc - 1, 2), np.int64)
+    tgroups = np.zeros((B, nc), np.int32)
+    lk = np.zeros((B, LK_SLOTS), np.int64)
+    S = np.zeros((nc, nc), np.float32)
+    Y = np.zeros((nc, nc), bool)
+    for b in range(B):
+        S[I, J] = probs[b, 1]
+        Y[I, J] = label[b, 1] > label[b, 0]
+        spq, sqp = S[iu, ju], S[ju, iu]
+        with np.errstate(invalid="ignore", over="ignore"):
+            if rule == "mean":
+                w = spq + sqp
+            elif rule == "any":
+                w = np.maximum(spq, sqp)
+            else:
+                w = np.minimum(spq, sqp)
+        nan = np.isnan(w)                          # either score, or inf + -inf under "mean"
+        w = np.where(w == 0, np.float32(0), w).astype(np.float32)       # -0 -> +0
+        ylink = Y[iu, ju] | Y[ju, iu]
+        t = _components(nc, iu[ylink], ju[ylink])
+        ntg = int(t.max()) + 1
+        ok = np.flatnonzero(~nan)
+        # (w descending, p ascending, q ascending); iu, ju are already in (p, q) order
+        order = ok[np.argsort(-w[ok].astype(np.float64), kind="stable")]
+        ep, eq, ew = iu[order], ju[order], w[order]
+        lab = np.arange(nc)                        # a cluster's label is its smallest member
+        hist = np.zeros((nc, ntg), np.int64)       # per cluster: members of each true group
+        hist[np.arange(nc), t] = 1
+        m = sp = ss = pos = 0
+        chunk = 4 * nc
+        while pos < len(order) and m < nc - 1:
+            # the sequential pass, with the edges already inside one cluster sieved out a
+            # chunk at a time (an edge inside a cluster stays inside it)
+            sel = np.flatnonzero(lab[ep[pos:pos + chunk]] != lab[eq[pos:pos + chunk]]) + pos
+            for e in sel:
+                a, c = lab[ep[e]], lab[eq[e]]
+                if a == c:
+                    continue
+                lo, hi = (a, c) if a < c else (c, a)
+                sp += int(hist[lo].sum() * hist[hi].sum())
+                ss += int(hist[lo] @ hist[hi])
+                hist[lo] += hist[hi]
+                lab[lab == hi] = lo
+                merges[b, m] = (ep[e], eq[e])
+                levels[b, m] = ew[e]
+                curve[b, m] = (sp, ss)
+                m += 1
+            pos += chunk
+            chunk *= 2
+        curve[b, m:] = (sp, ss)
+        tgroups[b] = t
+        lk[b, :5] = (m, ntg, np.count_nonzero(t[iu] == t[ju]), np.count_nonzero(nan),
+                     nc * (nc - 1) // 2)
+    return merges, levels, curve, tgroups, lk
+
+
+def _lk_arrays(levels, curve, lk):
+    levels = np.asarray(levels, np.float32)
+    levels = levels.reshape(-1, levels.shape[-1])
+    curve = np.asarray(curve).astype(np.int64).reshape(levels.shape + (2,))
+    lk = np.asarray(lk).astype(np.int64).reshape(-1, LK_SLOTS)
+    if len(lk) != len(levels):
+        raise ValueError("levels, curve and lk describe different numbers of commits")
+    return levels, curve, lk
+
+
+def curve_scores(levels, curve, lk):
+    """Per commit and per cut k (the partition after merges 0 .. k) -> dict of float64
+    (n_commits, Nc-1) arrays rand / precision / recall / f1, scores_from_untangle's ratios of
+    SS = SS_k, SD = SP_k - SS_k, DS = ST - SS_k, DD = PAIRS - SP_k - ST + SS_k (nan on a zero
+    denominator).  Rows k >= M repeat the last cut's scores."""
+    levels, curve, lk = _lk_arrays(levels, curve, lk)
+    sp, ss = curve[..., 0], curve[..., 1]
+    st, pairs = lk[:, LK_ST, None], lk[:, LK_PAIRS, None]
+    sd, ds = sp - ss, st - ss
+    dd = pairs - sp - st + ss
+    return {"rand": _ratio(ss + dd, ss + sd + ds + dd), "precision": _ratio(ss, ss + sd),
+            "recall": _ratio(ss, ss + ds), "f1": _ratio(2 * ss, 2 * ss + sd + ds)}
+
+
+def cut_table(levels, curve, lk, tprime):
+    """The (n_commits, UT_SLOTS) table hdg_untangle would give at the link bound t' (a pair
+    links iff its weight > t'), read off the linkage: per commit the merges with level > t'
+    are done.  UT_LINKS is -1: the tree does not know how many pairs link."""
+    levels, curve, lk = _lk_arrays(levels, curve, lk)
+    nc = levels.shape[1] + 1
+    with np.errstate(invalid="ignore"):
+        k = (levels > np.float32(tprime)).sum(1)              # NaN padding compares false
+    rows = np.arange(len(levels))
+    done = np.where(k[:, None] > 0, curve[rows, np.maximum(k, 1) - 1], 0)
+    sp, ss = done[:, 0], done[:, 1]
+    st, pairs = lk[:, LK_ST], lk[:, LK_PAIRS]
+    ut = np.zeros((len(levels), UT_SLOTS), np.int64)
+    ut[:, UT_GROUPS], ut[:, UT_TGROUPS] = nc - k, lk[:, LK_TGROUPS]
+    ut[:, UT_SS], ut[:, UT_SD], ut[:, UT_DS] = ss, sp - ss, st - ss
+    ut[:, UT_DD] = pairs - sp - st + ss
+    ut[:, UT_LINKS], ut[:, UT_NAN] = -1, lk[:, LK_NAN]
+    return ut
+
+
+def best_threshold(levels, curve, lk, rule, score="f1"):
+    """The link threshold with the best pooled score over the given commits, exactly:
+    -> (threshold, score, t').  The candidates for the link bound t' are every level of every
+    commit, and -inf; a candidate does, in each commit, the merges with level > t' (so the
+    largest level of all does none, and -inf does every merge above -inf).  The score is
+    scores_from_untangle's pooled `score` ("f1" or "rand") of the resulting tables, evaluated
+    at every candidate from one sort of all (level, dSP, dSS) events and their running sums.
+    A nan score never wins; ties go to the largest t' (if every score is nan: the largest
+    candidate, with a nan score).  threshold is what hdg_untangle takes: t' under "any" and
+    "both", 0.5 t' under "mean" (its bound is fl32(threshold + threshold)) -- exact unless t'
+    is an odd multiple of the smallest denormal: no float32 threshold doubles to such a
+    bound, 0.5 t' rounds, and hdg_untangle then cuts at a neighbouring denormal."""
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    if score not in ("f1", "rand"):
+        raise ValueError("score must be 'f1' or 'rand' (got %r)" % (score,))
+    levels, curve, lk = _lk_arrays(levels, curve, lk)
+    real = ~np.isnan(levels)
+    d = np.diff(curve, axis=1, prepend=0)                      # what merge k adds
+    lv = levels[real].astype(np.float64)
+    order = np.argsort(-lv, kind="stable")
+    lv = lv[order]
+    csp = np.concatenate([[0], np.cumsum(d[..., 0][real][order])])
+    css = np.concatenate([[0], np.cumsum(d[..., 1][real][order])])
+    # candidates, descending: each distinct level (done: the events before its first
+    # occurrence), then -inf (done: the events above -inf)
+    first = np.flatnonzero(np.concatenate([[True], lv[1:] != lv[:-1]])) if lv.size else \
+        np.zeros(0, np.int64)
+    cand = lv[first]
+    if not (cand.size and cand[-1] == -np.inf):
+        cand = np.concatenate([cand, [-np.inf]])
+        first = np.concatenate([first, [np.count_nonzero(lv > -np.inf)]])
+    sp, ss = csp[first], css[first]
+    st, pairs = int(lk[:, LK_ST].sum()), int(lk[:, LK_PAIRS].sum())
+    sd, ds = sp - ss, st - ss
+    dd = pairs - sp - st + ss
+    val = (_ratio(2 * ss, 2 * ss + sd + ds) if score == "f1"
+           else _ratio(ss + dd, ss + sd + ds + dd))
+    good = ~np.isnan(val)
+    i = int(np.flatnonzero(good & (val == val[good].max()))[0]) if good.any() else 0
+    tprime = np.float32(cand[i])
+    thr = np.float32(0.5) * tprime if rule == "mean" else tprime
+    return float(thr), float(val[i]), float(tprime)

@@ -650,6 +650,59 @@ class graph2graph(object):
             print('untangle nan pairs: %d' % scores["nan_pairs"])
         return scores, table, groups
 
+    # ------------------------------------------------------------------ calibrate
+    def calibrate(self, args, part="train", rule="mean", score="f1"):
+        """The link threshold untangle() should use: the one with the best pooled `score`
+        ("f1" | "rand") over the commits of the train (or test) split, exactly.  Per batch
+        Engine.forward then Engine.linkage (hdg_linkage), so only each commit's merge tree
+        and its integer curve (include/hdgnn.h, HDG_LK_*: Nc - 1 rows) come to the host,
+        never the probabilities; metrics.best_threshold does the rest.  Checkpoint, batches
+        and multi-rank gather as untangle().  -> (threshold, scores dict at that threshold
+        (metrics.scores_from_untangle of metrics.cut_table), levels float32 [n_commits][Nc-1],
+        curve int64 [n_commits][Nc-1][2], lk int64 [n_commits][8]); rank 0 prints the result
+        and writes linkage_levels<Ne>.npy, linkage_curve<Ne>.npy, linkage_merges<Ne>.npy and
+        linkage_counts<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/."""
+        import torch
+        if part not in ("train", "test"):
+            raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
+        _, _, train, test, maps = self._compact()
+        if self.load(self.checkpoint_dir):
+            print(" [*] Load SUCCESS")
+        else:
+            print(" [!] Load failed...")
+        eng = self.engine
+        outs = []
+        for db in self._device_batches(train if part == "train" else test, maps):
+            eng.forward(db)
+            m, lv, cv, _, lk = eng.linkage(db, rule=rule)
+            outs.append((m, lv, cv, lk))
+        nb, lb, n1 = len(outs), self.local_batch, self.Nc - 1
+        tails = ((n1, 2), (n1,), (n1, 2), (_lib.LK_SLOTS,))
+        dtypes = (np.int32, np.float32, np.int32, np.int64)
+        arrs = [(torch.stack([o[i] for o in outs]).cpu().numpy() if nb
+                 else np.zeros((0, lb) + tails[i], dtypes[i])) for i in range(4)]
+        eng.check_status()
+        if self.world > 1 and nb:      # rank-major (W nb, lb, ..) -> batch-major commit order
+            arrs = [self._gather(a).reshape((self.world, nb, lb) + tails[i])
+                    .transpose((1, 0, 2) + tuple(range(3, 3 + len(tails[i]))))
+                    for i, a in enumerate(arrs)]
+        merges, levels, curve, lk = (np.ascontiguousarray(a.reshape((-1,) + tails[i]))
+                                     for i, a in enumerate(arrs))
+        curve, lk = curve.astype(np.int64), lk.astype(np.int64)
+        threshold, best, tprime = metrics.best_threshold(levels, curve, lk, rule, score)
+        scores = metrics.scores_from_untangle(metrics.cut_table(levels, curve, lk, tprime))
+        if self.rank == 0:
+            step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
+            os.makedirs(step_dir, exist_ok=True)
+            np.save(step_dir + 'linkage_levels' + str(self.Ne) + '.npy', levels)
+            np.save(step_dir + 'linkage_curve' + str(self.Ne) + '.npy', curve)
+            np.save(step_dir + 'linkage_merges' + str(self.Ne) + '.npy', merges)
+            np.save(step_dir + 'linkage_counts' + str(self.Ne) + '.npy', lk)
+            print('calibrate rule: %s, part %s (%d commits)' % (rule, part, len(lk)))
+            print('calibrate score: %s = %s' % (score, best))
+            print('calibrate threshold: %r (link bound %r)' % (threshold, tprime))
+        return threshold, scores, levels, curve, lk
+
     # ------------------------------------------------------------------ test
     def test(self, args):
         _, C_edge_test, _, test, maps = self._compact()

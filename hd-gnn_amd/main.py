@@ -10,6 +10,9 @@ MI355X instead of a TF1 session.
                                                # of the trained model, computed on the device
     python hd-gnn_amd/main.py --Type untangle [--link-threshold 0.5 --link-rule mean]
                                                # hunk groups per commit and partition scores
+    python hd-gnn_amd/main.py --Type untangle --link-threshold auto [--link-score f1]
+                                               # ... at the threshold calibrated on the train split
+    python hd-gnn_amd/main.py --Type calibrate # that threshold alone (merge trees on the device)
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -31,18 +34,26 @@ def _init_distributed():
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local))
 
 
+def _threshold(text):
+    return text if text == 'auto' else float(text)
+
+
 def _variant(argv):
     """Additions to the reference's flags (every reference flag is unchanged):
     --model N (1..4, default 2 = the reference main.py's `from model_2 import`): which
     model_N.graph2graph to run; --loader utils2|fast: the reference's read_data (default)
     or hdgnn.loader reading the same dataset files straight into the compact form;
     --link-threshold T (default 0.5) and --link-rule mean|any|both (default mean): how
-    --Type untangle turns pair scores into links (include/hdgnn.h, hdg_untangle)."""
+    --Type untangle turns pair scores into links (include/hdgnn.h, hdg_untangle);
+    --link-threshold auto: the threshold with the best pooled --link-score f1|rand (default
+    f1) on the train split, from the commits' merge trees (hdg_linkage), which --Type
+    calibrate computes alone."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
-    p.add_argument('--link-threshold', type=float, default=0.5)
+    p.add_argument('--link-threshold', type=_threshold, default=0.5)
     p.add_argument('--link-rule', default='mean', choices=('mean', 'any', 'both'))
+    p.add_argument('--link-score', default='f1', choices=('f1', 'rand'))
     a, rest = p.parse_known_args(argv)
     return a, rest
 
@@ -115,7 +126,13 @@ def main(argv=None, model_cls=None):
         if args.Type == 'eval':      # not in the reference: on-device scores of the trained model
             model.evaluate(args)
         if args.Type == 'untangle':  # not in the reference: hunk groups per commit, on the device
-            model.untangle(args, threshold=extra.link_threshold, rule=extra.link_rule)
+            threshold = extra.link_threshold
+            if threshold == 'auto':
+                threshold = model.calibrate(args, part="train", rule=extra.link_rule,
+                                            score=extra.link_score)[0]
+            model.untangle(args, threshold=threshold, rule=extra.link_rule)
+        if args.Type == 'calibrate':  # not in the reference: the best link threshold, on the device
+            model.calibrate(args, part="train", rule=extra.link_rule, score=extra.link_score)
 
 
 if __name__ == '__main__':

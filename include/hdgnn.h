@@ -328,6 +328,68 @@ int    hdg_untangle(const hdg_shape* shape, const hdg_batch* batch, const float*
                     void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * On-device linkage (csrc/linkage.hip): the partition hdg_untangle gives is a step function
+ * of the threshold; hdg_linkage returns all its steps at once -- the single-linkage merge
+ * tree of each commit and the pair counts of every cut -- so the best threshold of a whole
+ * split follows on the host from nc - 1 rows per commit (hdgnn.metrics.best_threshold) and
+ * the probabilities never leave the device.
+ *
+ *   weight   of the unordered pair {p, q}, p < q, from hdg_untangle's scores s_pq, by `rule`:
+ *              HDG_UT_RULE_MEAN  w = fl32(s_pq + s_qp)
+ *              HDG_UT_RULE_ANY   w = max(s_pq, s_qp)
+ *              HDG_UT_RULE_BOTH  w = min(s_pq, s_qp)
+ *            a pair with a NaN in either direction is not an edge and counts in HDG_LK_NAN
+ *            (so does a pair whose weight is NaN from +inf and -inf under MEAN, which
+ *            hdg_untangle never links either but does not count in HDG_UT_NAN); a weight of
+ *            -0 is taken as +0.  hdg_untangle links {p, q} exactly when w > t',
+ *            t' = fl32(threshold + threshold) under MEAN and t' = threshold otherwise, so the
+ *            link graphs are the same
+ *   order    edges are ordered by (w descending, p ascending, q ascending): a total order
+ *   merges   the maximum spanning forest under that order is unique; its M <= nc - 1 edges in
+ *            that order (Kruskal's acceptance order) are the commit's merges, level[k] the
+ *            weight of merge k
+ *   cuts     after merges 0 .. k the partition is that of the link graph's components for
+ *            every t' with level[k+1] <= t' < level[k] (level[M] = -inf).  A state k with
+ *            level[k+1] == level[k] is reached by no threshold, nor is a merge at level -inf
+ *
+ *   merges   [batch][nc-1][2] i32, (p_k, q_k) with p < q; rows k >= M hold -1
+ *   levels   [batch][nc-1] f32; rows k >= M hold NaN
+ *   curve    [batch][nc-1][2] u32, (SP_k, SS_k): the unordered pairs in the same predicted
+ *            group after merges 0 .. k, and those of them that are also in the same true
+ *            group (true groups as hdg_untangle's); rows k >= M repeat row M - 1, or hold 0
+ *            when M = 0.  The group count after merge k is nc - (k + 1)
+ *   tgroups  [batch][nc] i32 true group ids as hdg_untangle's, or NULL
+ *   lk       [batch][HDG_LK_SLOTS] u64; with it DS_k = ST - SS_k, SD_k = SP_k - SS_k and
+ *            DD_k = PAIRS - SP_k - ST + SS_k
+ *   workspace  hdg_linkage_workspace_bytes(shape) bytes, 8-byte aligned; its content before
+ *            the call does not matter
+ * Every slot of every output is written by the call (nothing to zero).  Two launches on
+ * `stream` (k_lk_forest: hdg_untangle's blocks and tile pairs, each block reducing its tiles
+ * to a spanning forest by Boruvka rounds in LDS; k_lk_close: one block per commit reduces
+ * the blocks' forests to the commit's, sorts it, orders the hunks as the dendrogram's
+ * leaves and counts the pairs each merge joins), no host synchronisation, no block waits for
+ * another, no float atomics: the same bits on every run.  Only shape->batch, shape->nc and
+ * batch->ybits are read.  HDG_EINVAL (message in hdg_last_error) as hdg_untangle, without a
+ * threshold: batch outside [1, 65535], nc outside [2, 2048], an unknown rule, a NULL probs,
+ * merges, levels, curve, lk, workspace or ybits, or a workspace that is not 8-byte aligned. */
+#define HDG_LK_SLOTS 8
+#define HDG_LK_MERGES 0    /* M: edges of the commit's spanning forest                   */
+#define HDG_LK_TGROUPS 1   /* number of true groups                                      */
+#define HDG_LK_ST 2        /* unordered pairs in the same true group                     */
+#define HDG_LK_NAN 3       /* unordered pairs that are not edges (a NaN score)           */
+#define HDG_LK_PAIRS 4     /* nc (nc-1) / 2; slots 5 .. 7 are written as 0               */
+
+size_t hdg_linkage_workspace_bytes(const hdg_shape* shape);    /* 0 on a shape error */
+int    hdg_linkage(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                   int32_t rule,
+                   int32_t* merges   /* [batch][nc-1][2] */,
+                   float* levels     /* [batch][nc-1] */,
+                   uint32_t* curve   /* [batch][nc-1][2] */,
+                   int32_t* tgroups  /* [batch][nc] or NULL */,
+                   uint64_t* lk      /* [batch][HDG_LK_SLOTS] */,
+                   void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
  *
  * Instead of an RCCL call between hdg_fwd_bwd and hdg_adam_tf, the step's reduction
