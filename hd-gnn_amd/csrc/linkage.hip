@@ -19,20 +19,16 @@
 //                count go to the workspace.
 //   k_lk_close   grid B, 1024 threads.  Boruvka over the keys of the commit's block forests,
 //                a bitonic sort of the M survivors (descending: Kruskal's acceptance order)
-//                -> merges, levels; the true groups as k_ut_close builds them; the
-//                dendrogram order of the hunks (one thread walks the merges, appending the
-//                list of the cluster with the larger minimum to the other's tail and storing
-//                k on the boundary; the cluster's root under min-root hooking is its list's
-//                head); then two hunks at positions i < j join at merge
-//                max(boundary[i .. j-1]): every thread sweeps j upward from its i with a
-//                running maximum, counts pairs and same-true pairs in registers and flushes
-//                them to dSP[k] / dSS[k] when the maximum changes; an inclusive scan over k
-//                gives the curve.
+//                -> merges, levels; then the closing phase hdg_agglomerate shares
+//                (treeclose.h): the true groups as k_ut_close builds them, the dendrogram
+//                order of the hunks, the pairs each merge joins, and their inclusive scan
+//                over k, the curve.
 // Integer and bit results only; the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hdgnn_internal.h"
+#include "treeclose.h"
 #include "unionfind.h"
 
 namespace {
@@ -42,9 +38,7 @@ typedef unsigned long long u64;
 
 constexpr int LK_EPT = UT_T * UT_T / UT_LINK_NT;      // tile edges per thread of k_lk_forest
 constexpr int LK_MAX_ROUNDS = 32;                     // > ceil(log2 2048) + 1: never reached
-constexpr uint32_t LK_NEVER = 0xFFFFFFFFu;            // a boundary no merge crosses
 static_assert(UT_MAXN == 2048, "the key's low word packs p * 2048 + q");
-static_assert(UT_PER == 2, "the scan of the curve takes two rows per thread");
 
 // workspace, in 8-byte words per commit: nblk forests of nc - 1 keys, then nblk NaN counts
 __host__ __device__ inline size_t lk_commit_words(const int nc, const int nblk) {
@@ -155,11 +149,7 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_lk_forest(const float* __restric
       if (p < q && q < nc) {
         const float spq = sa[a * UT_LD + c], sqp = sb[c * UT_LD + a];
         float w;
-        if (rule == HDG_UT_RULE_MEAN) w = spq + sqp;
-        else if (rule == HDG_UT_RULE_ANY) w = spq > sqp ? spq : sqp;
-        else w = spq < sqp ? spq : sqp;
-        // a NaN score in either direction, or +inf and -inf under MEAN: not an edge
-        if (spq != spq || sqp != sqp || w != w) ++nans;
+        if (!ut_weight(rule, spq, sqp, w)) ++nans;
         else key[u] = lk_key(w, p, q);
       }
     }
@@ -210,17 +200,9 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_lk_close(const u64* __restrict_
   __shared__ u64 best[UT_MAXN];            // after the rounds: nxt | tail
   __shared__ uint32_t par[UT_MAXN];
   __shared__ uint32_t comp[UT_MAXN];       // then ut_label's ranks, then bnd
-  __shared__ uint32_t t[UT_MAXN];          // true group ids
-  __shared__ uint32_t bseq[UT_MAXN];       // bseq[i]: the merge that joins positions i, i + 1
-  __shared__ uint32_t tpos[UT_MAXN];       // true group of the hunk at position i
-  __shared__ uint32_t dsp[UT_MAXN];        // pairs first joined by merge k
-  __shared__ uint32_t dss[UT_MAXN];        // ... that are also in one true group
-  __shared__ uint32_t wsum[UT_CLOSE_WAVES];
-  __shared__ uint32_t wsum2[UT_CLOSE_WAVES][2];
-  __shared__ uint32_t red[UT_CLOSE_WAVES];
   __shared__ uint32_t count;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x;
   const int n1 = nc - 1;
   const u64* wb = ws + (size_t)b * lk_commit_words(nc, nblk);
@@ -275,152 +257,18 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_lk_close(const u64* __restrict_
     levels[o] = k < M ? lk_level(key) : __uint_as_float(0x7FC00000u);
   }
 
-  // ---- true groups: the set bits of the commit's label rows -------------------------------
-  for (int i = tid; i < nc; i += UT_CLOSE_NT) par[i] = (uint32_t)i;
-  __syncthreads();
-  ut_unite_labels(par, ybits + (size_t)b * nc * ((nc + 31) >> 5), nc);
-  __syncthreads();
-  const uint32_t TG = ut_label(par, comp, t, wsum, nc);
-  if (tgroups)
-    for (int i = tid; i < nc; i += UT_CLOSE_NT) tgroups[(size_t)b * nc + i] = (int32_t)t[i];
-
-  // ---- dendrogram order: one thread walks the merges ----------------------------------------
-  uint32_t* nxt = reinterpret_cast<uint32_t*>(best);
-  uint32_t* tail = nxt + UT_MAXN;
-  uint32_t* bnd = comp;
-  for (int i = tid; i < nc; i += UT_CLOSE_NT) {
-    par[i] = (uint32_t)i;
-    tail[i] = (uint32_t)i;
-    nxt[i] = LK_NEVER;
-    bnd[i] = LK_NEVER;
-    dsp[i] = 0u;
-    dss[i] = 0u;
-  }
-  __syncthreads();
-#ifdef HDG_LK_STAMP_WALK     // diagnostic build: the walk's 100 MHz ticks go to lk slot 7
-  u64 walk_ticks = 0;
-  if (tid == 0) walk_ticks = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (tid == 0) {
-    for (int k = 0; k < M; ++k) {
-      const u64 key = fk[k];
-      uint32_t x = lk_p(key), y = lk_q(key);
-      while (par[x] != x) {
-        par[x] = par[par[x]];
-        x = par[x];
-      }
-      while (par[y] != y) {
-        par[y] = par[par[y]];
-        y = par[y];
-      }
-      if (x == y) continue;                // not reached: the merges are a forest
-      const uint32_t lo = x < y ? x : y, hi = x < y ? y : x;
-      const uint32_t tl = tail[lo];
-      nxt[tl] = hi;                        // hi is the head of its list: its cluster's minimum
-      bnd[tl] = (uint32_t)k;
-      tail[lo] = tail[hi];
-      par[hi] = lo;
-    }
-    if (M < n1) {                          // several trees: chain them, no merge between them
-      uint32_t prev = 0;
-      for (int i = 1; i < nc; ++i)
-        if (par[i] == (uint32_t)i) {
-          nxt[tail[prev]] = (uint32_t)i;
-          prev = (uint32_t)i;
-        }
-    }
-    uint32_t node = 0;
-    for (int pos = 0; pos < nc && node < (uint32_t)nc; ++pos) {
-      tpos[pos] = t[node];
-      bseq[pos] = bnd[node];
-      node = nxt[node];
-    }
-  }
-#ifdef HDG_LK_STAMP_WALK
-  if (tid == 0) walk_ticks = __builtin_amdgcn_s_memrealtime() - walk_ticks;
-#endif
-  __syncthreads();
-
-  // ---- the pairs each merge joins: position i against every j > i --------------------------
-  uint32_t st = 0;
-  for (int i = tid; i < n1; i += UT_CLOSE_NT) {
-    const uint32_t ti = tpos[i];
-    uint32_t mx = bseq[i], cnt = 0, same = 0;
-    for (int j = i + 1; j < nc; ++j) {
-      const uint32_t bj = bseq[j - 1];
-      if (bj > mx) {
-        if (cnt && mx < (uint32_t)M) {
-          atomicAdd(&dsp[mx], cnt);
-          if (same) atomicAdd(&dss[mx], same);
-        }
-        mx = bj;
-        cnt = same = 0;
-      }
-      const uint32_t e = tpos[j] == ti;
-      ++cnt;
-      same += e;
-      st += e;
-    }
-    if (cnt && mx < (uint32_t)M) {
-      atomicAdd(&dsp[mx], cnt);
-      if (same) atomicAdd(&dss[mx], same);
-    }
-  }
-  st = ut_wave_sum(st);
-  if (lane == 0) red[wave] = st;
-  __syncthreads();
-
-  // ---- curve: inclusive scan over k, rows 2 tid and 2 tid + 1 ------------------------------
-  const int k0 = 2 * tid;
-  const uint32_t p0 = k0 < M ? dsp[k0] : 0u, p1 = k0 + 1 < M ? dsp[k0 + 1] : 0u;
-  const uint32_t s0 = k0 < M ? dss[k0] : 0u, s1 = k0 + 1 < M ? dss[k0 + 1] : 0u;
-  uint32_t ip = p0 + p1, is = s0 + s1;     // -> inclusive over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t vp = (uint32_t)__shfl_up((int)ip, o, 64), vs = (uint32_t)__shfl_up((int)is, o, 64);
-    if (lane >= o) {
-      ip += vp;
-      is += vs;
-    }
-  }
-  if (lane == 63) {
-    wsum2[wave][0] = ip;
-    wsum2[wave][1] = is;
-  }
-  __syncthreads();
-  uint32_t offp = 0, offs = 0, totp = 0, tots = 0;
-  for (int w = 0; w < UT_CLOSE_WAVES; ++w) {
-    const uint32_t vp = wsum2[w][0], vs = wsum2[w][1];
-    offp += w < wave ? vp : 0u;
-    offs += w < wave ? vs : 0u;
-    totp += vp;
-    tots += vs;
-  }
-  const uint32_t cp0 = offp + ip - p1, cs0 = offs + is - s1;     // row k0; row k0 + 1 adds p1, s1
-  uint32_t* cv = curve + (size_t)b * n1 * 2;
-  if (k0 < n1) {
-    cv[2 * k0] = k0 < M ? cp0 : totp;
-    cv[2 * k0 + 1] = k0 < M ? cs0 : tots;
-  }
-  if (k0 + 1 < n1) {
-    cv[2 * k0 + 2] = k0 + 1 < M ? cp0 + p1 : totp;
-    cv[2 * k0 + 3] = k0 + 1 < M ? cs0 + s1 : tots;
-  }
-  if (tid == 0) {
-    u64 sts = 0, nans = 0;
-    for (int w = 0; w < UT_CLOSE_WAVES; ++w) sts += red[w];
+  // ---- true groups, dendrogram order, pair counts, curve and the lk row: treeclose.h --------
+  unsigned long long nans = 0;             // fk is read-only from the sort's last barrier on
+  if (tid == 0)
     for (int f = 0; f < nblk; ++f) nans += wb[(size_t)nblk * n1 + f];
-    u64* row = lk + (size_t)b * HDG_LK_SLOTS;
-    row[HDG_LK_MERGES] = (u64)M;
-    row[HDG_LK_TGROUPS] = TG;
-    row[HDG_LK_ST] = sts;
-    row[HDG_LK_NAN] = nans;
-    row[HDG_LK_PAIRS] = (u64)nc * (u64)n1 / 2ull;
-    row[5] = row[6] = row[7] = 0ull;
-#ifdef HDG_LK_STAMP_WALK
-    row[7] = walk_ticks;
-#endif
-  }
+  tc_close(par, comp, reinterpret_cast<uint32_t*>(best),
+           [&](const int k, uint32_t& x, uint32_t& y) {
+             const u64 key = fk[k];
+             x = lk_p(key);
+             y = lk_q(key);
+           },
+           M, nans, ybits + (size_t)b * nc * ((nc + 31) >> 5), curve + (size_t)b * n1 * 2,
+           tgroups ? tgroups + (size_t)b * nc : nullptr, lk + (size_t)b * HDG_LK_SLOTS, nc);
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
-// unionfind.h -- the lock-free union-find in LDS, the component labelling and the tile
-// geometry that untangle.hip (hdg_untangle) and linkage.hip (hdg_linkage) share.
+// unionfind.h -- the lock-free union-find in LDS, the component labelling, the tile geometry
+// and the pair weight that untangle.hip (hdg_untangle), linkage.hip (hdg_linkage) and
+// agglo.hip (hdg_agglomerate, hdg_cut) share.
 //
 // Union-find, lock-free with min-root hooking.  Invariant: parent[i] <= i, and parent[i]
 // is always a node of i's own component.  find walks parent to a root (parent[r] == r) with
@@ -34,6 +35,19 @@ __host__ __device__ inline int ut_blocks(const int nc) {
   const int tiles = T * (T + 1) / 2;
   const int n = (tiles + HDG_UT_TILES_PER_BLOCK - 1) / HDG_UT_TILES_PER_BLOCK;
   return n < HDG_UT_MAX_BLOCKS ? n : HDG_UT_MAX_BLOCKS;
+}
+
+// The weight of the unordered pair {p, q} under `rule` from its two scores (include/hdgnn.h,
+// hdg_linkage) -> w, -0 taken as +0; false when the pair is not an edge: a NaN score in
+// either direction, or +inf and -inf under MEAN.  The one statement hdg_linkage and
+// hdg_agglomerate share.
+__device__ __forceinline__ bool ut_weight(const int rule, const float spq, const float sqp,
+                                          float& w) {
+  if (rule == HDG_UT_RULE_MEAN) w = spq + sqp;
+  else if (rule == HDG_UT_RULE_ANY) w = spq > sqp ? spq : sqp;
+  else w = spq < sqp ? spq : sqp;
+  if (__float_as_uint(w) == 0x80000000u) w = 0.f;
+  return !(spq != spq || sqp != sqp || w != w);
 }
 
 __device__ __forceinline__ uint32_t ut_ld(const uint32_t* p) {

@@ -71,6 +71,13 @@ UT_TILE, UT_TILES_PER_BLOCK, UT_MAX_BLOCKS = 64, 4, 16
 # hdg_linkage's per-commit row (include/hdgnn.h): lk[B][LK_SLOTS] u64
 LK_SLOTS = 8
 LK_MERGES, LK_TGROUPS, LK_ST, LK_NAN, LK_PAIRS = range(5)
+# hdg_agglomerate's methods and flags, hdg_cut's per-commit row (include/hdgnn.h)
+AG_SINGLE, AG_COMPLETE, AG_AVERAGE = 0, 1, 2
+AG_METHODS = {"single": AG_SINGLE, "complete": AG_COMPLETE, "average": AG_AVERAGE}
+AG_FLAG_GLOBAL = 1
+AG_LDS_MAX_NC = 256
+CUT_SLOTS = 8
+CUT_GROUPS, CUT_TGROUPS, CUT_SS, CUT_SD, CUT_DS, CUT_DD, CUT_MERGES, CUT_NAN = range(8)
 
 
 def untangle_blocks(nc):
@@ -96,7 +103,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_ckpt_writer_flush", "hdg_ckpt_writer_poll", "hdg_ckpt_writer_destroy", "hdg_memcpy_async",
            "hdg_event_create", "hdg_event_record", "hdg_event_synchronize", "hdg_event_destroy",
            "hdg_eval", "hdg_untangle_workspace_bytes", "hdg_untangle",
-           "hdg_linkage_workspace_bytes", "hdg_linkage"]
+           "hdg_linkage_workspace_bytes", "hdg_linkage",
+           "hdg_agglomerate_workspace_bytes", "hdg_agglomerate", "hdg_cut"]
 
 _lib = None
 
@@ -142,6 +150,11 @@ def load(path=None):
     lib.hdg_linkage_workspace_bytes.argtypes = [P(Shape)]
     lib.hdg_linkage_workspace_bytes.restype = ctypes.c_size_t
     lib.hdg_linkage.argtypes = [P(Shape), P(Batch), vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.hdg_agglomerate_workspace_bytes.argtypes = [P(Shape), i32]
+    lib.hdg_agglomerate_workspace_bytes.restype = ctypes.c_size_t
+    lib.hdg_agglomerate.argtypes = [P(Shape), P(Batch), vp, i32, i32, i32, vp, vp, vp, vp, vp,
+                                    vp, vp]
+    lib.hdg_cut.argtypes = [P(Shape), vp, vp, vp, vp, f32, i32, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

@@ -462,3 +462,73 @@ class Engine:
                                         ctypes.c_void_p(self._lk_workspace.data_ptr()),
                                         self._stream()))
         return merges, levels, curve, tgroups, lk
+
+    def agglomerate(self, dbatch, probs=None, rule="mean", method="average"):
+        """hdg_agglomerate: the merge tree of every commit under `method` ("single" |
+        "complete" | "average" linkage of the pair weights `rule` gives; include/hdgnn.h), in
+        linkage()'s format -> the same five fresh device tensors, so
+        hdgnn.metrics.best_threshold and cut() apply to them as they are.  `probs` as
+        untangle()'s.  Enqueued on the current stream; nothing is copied to the host.  The
+        workspace is allocated on the first call and kept."""
+        self._check(dbatch)
+        probs = self.probs if probs is None else probs
+        if (probs.device != self.device or probs.dtype != torch.float32
+                or not probs.is_contiguous()
+                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
+            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
+                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        if rule not in _lib.UT_RULES:
+            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        if method not in _lib.AG_METHODS:
+            raise ValueError("method must be one of %s (got %r)"
+                             % (", ".join(_lib.AG_METHODS), method))
+        if getattr(self, "_ag_workspace", None) is None:
+            nbytes = self.lib.hdg_agglomerate_workspace_bytes(ctypes.byref(self.shape), 0)
+            if nbytes == 0:
+                raise RuntimeError(self.lib.hdg_last_error().decode())
+            self._ag_workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        n1 = self.nc - 1
+        merges = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
+        levels = torch.empty(self.batch, n1, dtype=torch.float32, device=self.device)
+        curve = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
+        tgroups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
+        lk = torch.empty(self.batch, _lib.LK_SLOTS, dtype=torch.int64, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_agglomerate(ctypes.byref(self.shape), ctypes.byref(b),
+                                            ctypes.c_void_p(probs.data_ptr()),
+                                            _lib.UT_RULES[rule], _lib.AG_METHODS[method], 0,
+                                            ctypes.c_void_p(merges.data_ptr()),
+                                            ctypes.c_void_p(levels.data_ptr()),
+                                            ctypes.c_void_p(curve.data_ptr()),
+                                            ctypes.c_void_p(tgroups.data_ptr()),
+                                            ctypes.c_void_p(lk.data_ptr()),
+                                            ctypes.c_void_p(self._ag_workspace.data_ptr()),
+                                            self._stream()))
+        return merges, levels, curve, tgroups, lk
+
+    def cut(self, merges, levels, curve, lk, threshold=0.5, rule="mean"):
+        """hdg_cut: the groups the merge tree (merges, levels, curve, lk as linkage() or
+        agglomerate() returned them) gives at `threshold` under `rule`, the threshold meaning
+        what it means to untangle() -> (groups int32 [B][nc], ut int64 [B][CUT_SLOTS]) as
+        fresh device tensors; ut has untangle()'s slots except CUT_MERGES, the merges done
+        (hdgnn.metrics.scores_from_untangle reads it as it is).  Enqueued on the current
+        stream; nothing is copied to the host."""
+        n1 = self.nc - 1
+        want = ((merges, torch.int32, (self.batch, n1, 2)), (levels, torch.float32, (self.batch, n1)),
+                (curve, torch.int32, (self.batch, n1, 2)), (lk, torch.int64, (self.batch, _lib.LK_SLOTS)))
+        for x, dt, shp in want:
+            if (x.device != self.device or x.dtype != dt or not x.is_contiguous()
+                    or tuple(x.shape) != shp):
+                raise ValueError("merges, levels, curve and lk must be the contiguous tensors "
+                                 "linkage() / agglomerate() return for this engine")
+        if rule not in _lib.UT_RULES:
+            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        groups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
+        ut = torch.empty(self.batch, _lib.CUT_SLOTS, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.hdg_cut(ctypes.byref(self.shape), ctypes.c_void_p(merges.data_ptr()),
+                                    ctypes.c_void_p(levels.data_ptr()),
+                                    ctypes.c_void_p(curve.data_ptr()),
+                                    ctypes.c_void_p(lk.data_ptr()), ctypes.c_float(threshold),
+                                    _lib.UT_RULES[rule], ctypes.c_void_p(groups.data_ptr()),
+                                    ctypes.c_void_p(ut.data_ptr()), self._stream()))
+        return groups, ut

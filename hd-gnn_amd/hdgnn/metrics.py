@@ -454,3 +454,119 @@ def best_threshold(levels, curve, lk, rule, score="f1"):
     tprime = np.float32(cand[i])
     thr = np.float32(0.5) * tprime if rule == "mean" else tprime
     return float(thr), float(val[i]), float(tprime)
+
+
+# ---------------------------------------------------------------------------------------
+# Agglomeration: the merge tree of a commit under single, complete or average linkage, as
+# hdg_agglomerate computes it on the device (include/hdgnn.h, HDG_AG_*), its host
+# restatement, and the groups any merge tree gives at a link bound (hdg_cut).
+# ---------------------------------------------------------------------------------------
+AG_METHODS = ("single", "complete", "average")
+
+
+def agglomerate(label_onehot, probs, rule="mean", method="average", raw=False):
+    """(B, 2, R) one-hot labels and probabilities -> linkage()'s five outputs for the merge
+    tree under `method` ("single" | "complete" | "average"), the host restatement of
+    hdg_agglomerate, definitions as in include/hdgnn.h; with raw=True a sixth, the raw levels
+    float32 (B, Nc-1) before the running minimum.  Plain: the full cluster-pair matrix (float32
+    weights, or sums under "average"; NaN is no edge), and per step one arg-max over the whole
+    matrix in the order (D descending, a, c) -- under "average" over the float64 quotients
+    S / (|A| |C|) -- then row and column a are recombined (max ignoring NaN / min keeping NaN /
+    one float32 addition) and c is retired.  The curve comes from the clusters' true-group
+    histograms as in linkage()."""
+    from .data import pair_index
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    if method not in AG_METHODS:
+        raise ValueError("method must be one of %s (got %r)" % (", ".join(AG_METHODS), method))
+    label = np.asarray(label_onehot)
+    probs = np.asarray(probs, np.float32)
+    B, R = probs.shape[0], probs.shape[2]
+    nc = _nc_of(R)
+    I, J = pair_index(nc)
+    iu, ju = np.triu_indices(nc, 1)
+    merges = np.full((B, nc - 1, 2), -1, np.int32)
+    levels = np.full((B, nc - 1), np.nan, np.float32)
+    rawlv = np.full((B, nc - 1), np.nan, np.float32)
+    curve = np.zeros((B, nc - 1, 2), np.int64)
+    tgroups = np.zeros((B, nc), np.int32)
+    lk = np.zeros((B, LK_SLOTS), np.int64)
+    S = np.zeros((nc, nc), np.float32)
+    Y = np.zeros((nc, nc), bool)
+    upper = np.triu(np.ones((nc, nc), bool), 1)
+    for b in range(B):
+        S[I, J] = probs[b, 1]
+        Y[I, J] = label[b, 1] > label[b, 0]
+        with np.errstate(invalid="ignore", over="ignore"):
+            if rule == "mean":
+                W = S + S.T
+            elif rule == "any":
+                W = np.maximum(S, S.T)                 # NaN when either is
+            else:
+                W = np.minimum(S, S.T)
+        W = np.where(W == 0, np.float32(0), W).astype(np.float32)       # -0 -> +0
+        np.fill_diagonal(W, np.nan)
+        nans = int(np.count_nonzero(np.isnan(W[iu, ju])))
+        ylink = Y[iu, ju] | Y[ju, iu]
+        t = _components(nc, iu[ylink], ju[ylink])
+        ntg = int(t.max()) + 1
+        hist = np.zeros((nc, ntg), np.int64)
+        hist[np.arange(nc), t] = 1
+        size = np.ones(nc, np.int64)
+        live = np.ones(nc, bool)
+        m = sp = ss = 0
+        low = None
+        while m < nc - 1:
+            with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                V = (W.astype(np.float64) / np.outer(size, size).astype(np.float64)
+                     if method == "average" else W.astype(np.float64))
+            ok = upper & live[:, None] & live[None, :] & ~np.isnan(V)
+            cand = np.flatnonzero(ok.ravel())          # row-major: (a, c) ascending
+            if not cand.size:
+                break
+            j = int(cand[np.argmax(V.ravel()[cand])])  # the first of the largest
+            a, c = divmod(j, nc)
+            r = np.float32(V[a, c])
+            low = r if low is None or r < low else low
+            merges[b, m] = (a, c)
+            rawlv[b, m], levels[b, m] = r, low
+            sp += int(size[a] * size[c])
+            ss += int(hist[a] @ hist[c])
+            curve[b, m] = (sp, ss)
+            with np.errstate(invalid="ignore", over="ignore"):
+                if method == "average":
+                    n = W[a] + W[c]
+                elif method == "single":
+                    n = np.fmax(W[a], W[c])
+                else:
+                    n = np.minimum(W[a], W[c])
+            W[a, :] = W[:, a] = n
+            W[c, :] = W[:, c] = np.nan
+            W[a, a] = np.nan
+            hist[a] += hist[c]
+            size[a] += size[c]
+            live[c] = False
+            m += 1
+        curve[b, m:] = (sp, ss)
+        tgroups[b] = t
+        lk[b, :5] = (m, ntg, np.count_nonzero(t[iu] == t[ju]), nans, nc * (nc - 1) // 2)
+    out = (merges, levels, curve, tgroups, lk)
+    return out + (rawlv,) if raw else out
+
+
+def cut_groups(merges, levels, tprime):
+    """Merges int (n, Nc-1, 2) and levels float32 (n, Nc-1) of any merge tree -> int32
+    (n, Nc) groups at the link bound t': per commit the merges with level > t' are united
+    (rows of -1 / NaN are skipped); ids dense, ordered by smallest member -- what hdg_cut
+    writes."""
+    merges = np.asarray(merges)
+    levels = np.asarray(levels, np.float32)
+    levels = levels.reshape(-1, levels.shape[-1])
+    merges = merges.reshape(levels.shape + (2,)).astype(np.int64)
+    nc = levels.shape[1] + 1
+    groups = np.zeros((len(levels), nc), np.int32)
+    with np.errstate(invalid="ignore"):
+        take = (levels > np.float32(tprime)) & (merges >= 0).all(-1)
+    for b in range(len(levels)):
+        groups[b] = _components(nc, merges[b, take[b], 0], merges[b, take[b], 1])
+    return groups

@@ -599,7 +599,7 @@ class graph2graph(object):
         return scores, table
 
     # ------------------------------------------------------------------ untangle
-    def untangle(self, args, part="test", threshold=0.5, rule="mean"):
+    def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single"):
         """Untangle the commits of the test (or train) split with the trained classifier: per
         batch Engine.forward then Engine.untangle (hdg_untangle), so only each commit's hunk
         group ids and its integer row (include/hdgnn.h, HDG_UT_*) come to the host, never the
@@ -607,10 +607,17 @@ class graph2graph(object):
         evaluate(): the checkpoint from where train() saves it, the batches of test().
         -> (scores dict, int64 table [n_commits][8], int32 groups [n_commits][Nc]); rank 0
         prints the scores (metrics.scores_from_untangle) and writes untangle_groups<Ne>.npy
-        and untangle_counts<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/."""
+        and untangle_counts<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/.
+        method "complete" | "average": the groups are the cut at `threshold` of each commit's
+        merge tree under that linkage instead (Engine.agglomerate then Engine.cut: hdg_cut's
+        row, whose slot 6 holds the merges done, not the linked pairs); "single" is
+        hdg_untangle, the link graph's components."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
+        if method not in _lib.AG_METHODS:
+            raise ValueError("method must be one of %s (got %r)"
+                             % (", ".join(_lib.AG_METHODS), method))
         _, _, train, test, maps = self._compact()
         if self.load(self.checkpoint_dir):
             print(" [*] Load SUCCESS")
@@ -620,7 +627,11 @@ class graph2graph(object):
         rows, ids = [], []
         for db in self._device_batches(train if part == "train" else test, maps):
             eng.forward(db)
-            g, ut = eng.untangle(db, threshold=threshold, rule=rule)
+            if method == "single":
+                g, ut = eng.untangle(db, threshold=threshold, rule=rule)
+            else:
+                m, lv, cv, _, lk = eng.agglomerate(db, rule=rule, method=method)
+                g, ut = eng.cut(m, lv, cv, lk, threshold=threshold, rule=rule)
             ids.append(g)
             rows.append(ut)
         nb, lb = len(rows), self.local_batch
@@ -642,6 +653,8 @@ class graph2graph(object):
             np.save(step_dir + 'untangle_groups' + str(self.Ne) + '.npy', groups)
             np.save(step_dir + 'untangle_counts' + str(self.Ne) + '.npy', table)
             print('untangle rule: %s, threshold %s' % (rule, threshold))
+            if method != "single":
+                print('untangle method: %s' % method)
             for name in ("rand", "precision", "recall", "f1"):
                 print('untangle %s: %s (per-commit mean %s)' % (name, scores[name],
                                                                 scores[name + "_mean"]))
@@ -651,7 +664,7 @@ class graph2graph(object):
         return scores, table, groups
 
     # ------------------------------------------------------------------ calibrate
-    def calibrate(self, args, part="train", rule="mean", score="f1"):
+    def calibrate(self, args, part="train", rule="mean", score="f1", method="single"):
         """The link threshold untangle() should use: the one with the best pooled `score`
         ("f1" | "rand") over the commits of the train (or test) split, exactly.  Per batch
         Engine.forward then Engine.linkage (hdg_linkage), so only each commit's merge tree
@@ -661,10 +674,16 @@ class graph2graph(object):
         (metrics.scores_from_untangle of metrics.cut_table), levels float32 [n_commits][Nc-1],
         curve int64 [n_commits][Nc-1][2], lk int64 [n_commits][8]); rank 0 prints the result
         and writes linkage_levels<Ne>.npy, linkage_curve<Ne>.npy, linkage_merges<Ne>.npy and
-        linkage_counts<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/."""
+        linkage_counts<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/.
+        method "complete" | "average": the trees are Engine.agglomerate's under that linkage
+        (hdg_agglomerate) and the threshold is the one untangle(method=...) should use; the
+        files are agglo_<method>_levels<Ne>.npy, _curve, _merges and _counts."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
+        if method not in _lib.AG_METHODS:
+            raise ValueError("method must be one of %s (got %r)"
+                             % (", ".join(_lib.AG_METHODS), method))
         _, _, train, test, maps = self._compact()
         if self.load(self.checkpoint_dir):
             print(" [*] Load SUCCESS")
@@ -674,7 +693,8 @@ class graph2graph(object):
         outs = []
         for db in self._device_batches(train if part == "train" else test, maps):
             eng.forward(db)
-            m, lv, cv, _, lk = eng.linkage(db, rule=rule)
+            m, lv, cv, _, lk = (eng.linkage(db, rule=rule) if method == "single"
+                                else eng.agglomerate(db, rule=rule, method=method))
             outs.append((m, lv, cv, lk))
         nb, lb, n1 = len(outs), self.local_batch, self.Nc - 1
         tails = ((n1, 2), (n1,), (n1, 2), (_lib.LK_SLOTS,))
@@ -694,11 +714,14 @@ class graph2graph(object):
         if self.rank == 0:
             step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
             os.makedirs(step_dir, exist_ok=True)
-            np.save(step_dir + 'linkage_levels' + str(self.Ne) + '.npy', levels)
-            np.save(step_dir + 'linkage_curve' + str(self.Ne) + '.npy', curve)
-            np.save(step_dir + 'linkage_merges' + str(self.Ne) + '.npy', merges)
-            np.save(step_dir + 'linkage_counts' + str(self.Ne) + '.npy', lk)
+            stem = step_dir + ('linkage_' if method == "single" else 'agglo_%s_' % method)
+            np.save(stem + 'levels' + str(self.Ne) + '.npy', levels)
+            np.save(stem + 'curve' + str(self.Ne) + '.npy', curve)
+            np.save(stem + 'merges' + str(self.Ne) + '.npy', merges)
+            np.save(stem + 'counts' + str(self.Ne) + '.npy', lk)
             print('calibrate rule: %s, part %s (%d commits)' % (rule, part, len(lk)))
+            if method != "single":
+                print('calibrate method: %s' % method)
             print('calibrate score: %s = %s' % (score, best))
             print('calibrate threshold: %r (link bound %r)' % (threshold, tprime))
         return threshold, scores, levels, curve, lk

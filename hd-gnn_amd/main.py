@@ -13,6 +13,9 @@ MI355X instead of a TF1 session.
     python hd-gnn_amd/main.py --Type untangle --link-threshold auto [--link-score f1]
                                                # ... at the threshold calibrated on the train split
     python hd-gnn_amd/main.py --Type calibrate # that threshold alone (merge trees on the device)
+    python hd-gnn_amd/main.py --Type calibrate --link-method average
+    python hd-gnn_amd/main.py --Type untangle --link-threshold auto --link-method complete
+                                               # groups from complete / average linkage trees
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -47,13 +50,15 @@ def _variant(argv):
     --Type untangle turns pair scores into links (include/hdgnn.h, hdg_untangle);
     --link-threshold auto: the threshold with the best pooled --link-score f1|rand (default
     f1) on the train split, from the commits' merge trees (hdg_linkage), which --Type
-    calibrate computes alone."""
+    calibrate computes alone; --link-method single|complete|average (default single: the link
+    graph's components): the linkage whose merge tree both cut (hdg_agglomerate, hdg_cut)."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
     p.add_argument('--link-threshold', type=_threshold, default=0.5)
     p.add_argument('--link-rule', default='mean', choices=('mean', 'any', 'both'))
     p.add_argument('--link-score', default='f1', choices=('f1', 'rand'))
+    p.add_argument('--link-method', default='single', choices=('single', 'complete', 'average'))
     a, rest = p.parse_known_args(argv)
     return a, rest
 
@@ -125,14 +130,17 @@ def main(argv=None, model_cls=None):
             model.test(args)
         if args.Type == 'eval':      # not in the reference: on-device scores of the trained model
             model.evaluate(args)
+        # single linkage is the call as it always was; another method is passed on
+        how = {} if extra.link_method == 'single' else {'method': extra.link_method}
         if args.Type == 'untangle':  # not in the reference: hunk groups per commit, on the device
             threshold = extra.link_threshold
             if threshold == 'auto':
                 threshold = model.calibrate(args, part="train", rule=extra.link_rule,
-                                            score=extra.link_score)[0]
-            model.untangle(args, threshold=threshold, rule=extra.link_rule)
+                                            score=extra.link_score, **how)[0]
+            model.untangle(args, threshold=threshold, rule=extra.link_rule, **how)
         if args.Type == 'calibrate':  # not in the reference: the best link threshold, on the device
-            model.calibrate(args, part="train", rule=extra.link_rule, score=extra.link_score)
+            model.calibrate(args, part="train", rule=extra.link_rule, score=extra.link_score,
+                            **how)
 
 
 if __name__ == '__main__':

@@ -390,6 +390,101 @@ int    hdg_linkage(const hdg_shape* shape, const hdg_batch* batch, const float* 
                    void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * On-device agglomeration (csrc/agglo.hip): hdg_linkage's tree is single linkage, which
+ * chains -- one wrong high score between two groups fuses them at every threshold below
+ * it.  hdg_agglomerate builds the merge tree of each commit under single, complete or
+ * average linkage (UPGMA) in hdg_linkage's output format, and hdg_cut turns any such tree
+ * into groups at a threshold, so best_threshold, cut_table and calibration apply unchanged.
+ *
+ *   weight   w of the unordered pair {p, q} under `rule`, and the pairs that are not edges:
+ *            exactly hdg_linkage's (a NaN score in either direction, NaN from +inf and -inf
+ *            under MEAN, -0 taken as +0; they count in HDG_LK_NAN)
+ *   clusters start as the nc singletons; a cluster is named by its smallest member.  The
+ *            similarity D(A, C) of two clusters, by `method`:
+ *              HDG_AG_SINGLE    the largest weight over the pairs between them that are
+ *                               edges; no edge when none of them is
+ *              HDG_AG_COMPLETE  the smallest weight over the pairs between them; no edge when
+ *                               any pair between them is no edge
+ *              HDG_AG_AVERAGE   v = (double)S / (double)(|A| |C|), one IEEE double division;
+ *                               S of two singletons is the pair's fp32 weight and
+ *                               S(A u C, X) = fl32(S(A, X) + S(C, X)), one fp32 addition
+ *                               (commutative: the value depends on the merge tree alone); no
+ *                               edge when either summand is no edge or the sum is NaN
+ *   step     among all cluster pairs (a, c), a < c, that have an edge, the first under
+ *            (D descending, a ascending, c ascending) -- under AVERAGE D is compared as the
+ *            double v -- merges: a absorbs c.  Its raw level r_k is D as fp32 ((float)v under
+ *            AVERAGE); merges[k] = (a, c), levels[k] = min(r_0 .. r_k).  Steps repeat until no
+ *            cluster pair has an edge: M <= nc - 1
+ *   levels   are non-increasing by construction.  Under SINGLE and COMPLETE the raw levels
+ *            already are; under AVERAGE they can invert by an ulp through the fp32 sums.
+ *            With the running minimum "the merges with level > t'" is a prefix of the merges:
+ *            what a greedy agglomeration stopped at the first best similarity <= t' has done
+ *   curve, tgroups, lk and the padding of rows k >= M: hdg_linkage's, slot for slot
+ *   SINGLE   gives hdg_linkage's levels bit for bit and its curve at every k with
+ *            level[k+1] < level[k]; the merge pairs differ (cluster minima here, edge ends
+ *            there)
+ *   workspace  hdg_agglomerate_workspace_bytes(shape, flags) bytes (batch * nc * nc floats),
+ *            8-byte aligned; its content before the call does not matter
+ * Three launches on `stream`: k_ag_weights (one block per 64 x 64 tile pair of a commit,
+ * hdg_untangle's staging) writes the commit's pair weights, packed by rows of the upper
+ * triangle, into the commit's region of the workspace; k_ag_merge, one block per commit,
+ * keeps the cluster-pair matrix in LDS for nc <= HDG_AG_LDS_MAX_NC and works on the
+ * workspace copy above that (HDG_AG_FLAG_GLOBAL forces the latter at any nc: a test and
+ * diagnostic flag, the results are bit-identical), each live row caching its best partner;
+ * k_ag_close is hdg_linkage's closing phase.  No host synchronisation, no block waits for
+ * another, no float atomics: the same bits on every run.  The step loop is bounded by
+ * nc - 1 and every inner loop by nc.  Only shape->batch, shape->nc and batch->ybits are
+ * read.  Every slot of every output is written by the call.  HDG_EINVAL (message in
+ * hdg_last_error) for what hdg_linkage rejects, an unknown method or an unknown flag bit;
+ * nothing is launched then.                                                               */
+#define HDG_AG_SINGLE 0
+#define HDG_AG_COMPLETE 1
+#define HDG_AG_AVERAGE 2
+#define HDG_AG_FLAG_GLOBAL 1       /* keep the cluster-pair matrix in the workspace        */
+#define HDG_AG_LDS_MAX_NC 256      /* largest nc whose matrix k_ag_merge keeps in LDS: 32640
+                                      floats of the 160 KiB, the rest for its row caches   */
+
+/* 0 on a shape error only; the size is the same under every flag */
+size_t hdg_agglomerate_workspace_bytes(const hdg_shape* shape, int32_t flags);
+int    hdg_agglomerate(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                       int32_t rule, int32_t method, int32_t flags,
+                       int32_t* merges   /* [batch][nc-1][2] */,
+                       float* levels     /* [batch][nc-1] */,
+                       uint32_t* curve   /* [batch][nc-1][2] */,
+                       int32_t* tgroups  /* [batch][nc] or NULL */,
+                       uint64_t* lk      /* [batch][HDG_LK_SLOTS] */,
+                       void* workspace, void* stream);
+
+/* hdg_cut: the groups of a merge tree (hdg_linkage's or hdg_agglomerate's) at a threshold.
+ * With t' from (threshold, rule) as hdg_untangle forms it (fl32(threshold + threshold) under
+ * MEAN, threshold otherwise), per commit the merges with levels[k] > t' are united; rows of
+ * -1 / NaN are skipped.  groups gets hdg_untangle's dense ids, ordered by smallest member.
+ * With `ut` given, `curve` and `lk` are required and the row holds hdg_untangle's slots
+ * (HDG_CUT_GROUPS .. HDG_CUT_DD as HDG_UT_GROUPS .. HDG_UT_DD) read off curve[k-1] and lk
+ * for the k merges done -- except slot HDG_CUT_MERGES, which holds k (a tree does not know
+ * the linked pairs), and HDG_CUT_NAN, which is lk's HDG_LK_NAN (it also counts a pair of
+ * +inf and -inf under MEAN, which HDG_UT_NAN does not).  On hdg_linkage's tree the groups
+ * and the other slots are hdg_untangle's at the same threshold.  One launch, one block per
+ * commit, only shape->batch and shape->nc are read.  HDG_EINVAL for a bad shape, a NaN
+ * threshold, an unknown rule, a NULL merges, levels or groups, or ut without curve and lk. */
+#define HDG_CUT_SLOTS 8
+#define HDG_CUT_GROUPS 0
+#define HDG_CUT_TGROUPS 1
+#define HDG_CUT_SS 2
+#define HDG_CUT_SD 3
+#define HDG_CUT_DS 4
+#define HDG_CUT_DD 5
+#define HDG_CUT_MERGES 6   /* merges done: the rows with level > t'                      */
+#define HDG_CUT_NAN 7      /* lk's HDG_LK_NAN                                            */
+
+int    hdg_cut(const hdg_shape* shape, const int32_t* merges, const float* levels,
+               const uint32_t* curve /* or NULL */, const uint64_t* lk /* or NULL */,
+               float threshold, int32_t rule,
+               int32_t* groups   /* [batch][nc] */,
+               uint64_t* ut      /* [batch][HDG_CUT_SLOTS] or NULL */,
+               void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
  *
  * Instead of an RCCL call between hdg_fwd_bwd and hdg_adam_tf, the step's reduction
