@@ -78,6 +78,12 @@ AG_FLAG_GLOBAL = 1
 AG_LDS_MAX_NC = 256
 CUT_SLOTS = 8
 CUT_GROUPS, CUT_TGROUPS, CUT_SS, CUT_SD, CUT_DS, CUT_DD, CUT_MERGES, CUT_NAN = range(8)
+# hdg_refine's per-commit rows (include/hdgnn.h): ut[B][RF_SLOTS] u64 (slots 0 .. 5 as UT_*),
+# rq[B][RF_Q_SLOTS] i64
+RF_SLOTS, RF_MOVES, RF_NAN = 8, 6, 7
+RF_Q_SLOTS = 4
+RF_Q_START, RF_Q_END, RF_Q_SWEEPS, RF_Q_CONVERGED = range(4)
+RF_MAX_SWEEPS = 64
 
 
 def untangle_blocks(nc):
@@ -104,7 +110,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_event_create", "hdg_event_record", "hdg_event_synchronize", "hdg_event_destroy",
            "hdg_eval", "hdg_untangle_workspace_bytes", "hdg_untangle",
            "hdg_linkage_workspace_bytes", "hdg_linkage",
-           "hdg_agglomerate_workspace_bytes", "hdg_agglomerate", "hdg_cut"]
+           "hdg_agglomerate_workspace_bytes", "hdg_agglomerate", "hdg_cut",
+           "hdg_refine_workspace_bytes", "hdg_refine"]
 
 _lib = None
 
@@ -155,6 +162,9 @@ def load(path=None):
     lib.hdg_agglomerate.argtypes = [P(Shape), P(Batch), vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                     vp, vp]
     lib.hdg_cut.argtypes = [P(Shape), vp, vp, vp, vp, f32, i32, vp, vp, vp]
+    lib.hdg_refine_workspace_bytes.argtypes = [P(Shape), i32]
+    lib.hdg_refine_workspace_bytes.restype = ctypes.c_size_t
+    lib.hdg_refine.argtypes = [P(Shape), P(Batch), vp, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

@@ -532,3 +532,54 @@ class Engine:
                                     _lib.UT_RULES[rule], ctypes.c_void_p(groups.data_ptr()),
                                     ctypes.c_void_p(ut.data_ptr()), self._stream()))
         return groups, ut
+
+    def refine(self, dbatch, groups=None, probs=None, threshold=0.5, rule="mean", max_sweeps=8):
+        """hdg_refine: best-move sweeps on the correlation-clustering objective of `probs`
+        under `rule` at `threshold` (the threshold meaning what it means to untangle();
+        include/hdgnn.h), starting from `groups` (int32 [B][nc] on this device, as untangle()
+        or cut() returned them; None: every hunk alone), at most `max_sweeps` sweeps ->
+        (groups int32 [B][nc], ut int64 [B][RF_SLOTS], rq int64 [B][RF_Q_SLOTS]) as fresh
+        device tensors; ut has untangle()'s slots except RF_MOVES, the moves made
+        (hdgnn.metrics.scores_from_untangle reads it as it is), rq holds the objective at the
+        start and the end, the sweeps run and whether the last one made no move.  `probs` as
+        untangle()'s.  Enqueued on the current stream; nothing is copied to the host.  The
+        workspace is allocated on the first call and kept."""
+        self._check(dbatch)
+        probs = self.probs if probs is None else probs
+        if (probs.device != self.device or probs.dtype != torch.float32
+                or not probs.is_contiguous()
+                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
+            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
+                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        if rule not in _lib.UT_RULES:
+            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        if not (isinstance(max_sweeps, int) and 1 <= max_sweeps <= _lib.RF_MAX_SWEEPS):
+            raise ValueError("max_sweeps must be an int in [1, %d] (got %r)"
+                             % (_lib.RF_MAX_SWEEPS, max_sweeps))
+        if groups is not None and (groups.device != self.device or groups.dtype != torch.int32
+                                   or not groups.is_contiguous()
+                                   or tuple(groups.shape) != (self.batch, self.nc)):
+            raise ValueError("groups must be a contiguous int32 [%d][%d] tensor on %s"
+                             % (self.batch, self.nc, self.device))
+        if getattr(self, "_rf_workspace", None) is None:
+            nbytes = self.lib.hdg_refine_workspace_bytes(ctypes.byref(self.shape), 0)
+            if nbytes == 0:
+                raise RuntimeError(self.lib.hdg_last_error().decode())
+            self._rf_workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        out = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
+        # u64 counts, every value < 2^63: int64 reads them as they are
+        ut = torch.empty(self.batch, _lib.RF_SLOTS, dtype=torch.int64, device=self.device)
+        rq = torch.empty(self.batch, _lib.RF_Q_SLOTS, dtype=torch.int64, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_refine(ctypes.byref(self.shape), ctypes.byref(b),
+                                       ctypes.c_void_p(probs.data_ptr()),
+                                       ctypes.c_float(threshold), _lib.UT_RULES[rule],
+                                       max_sweeps, 0,
+                                       None if groups is None
+                                       else ctypes.c_void_p(groups.data_ptr()),
+                                       ctypes.c_void_p(out.data_ptr()),
+                                       ctypes.c_void_p(ut.data_ptr()),
+                                       ctypes.c_void_p(rq.data_ptr()),
+                                       ctypes.c_void_p(self._rf_workspace.data_ptr()),
+                                       self._stream()))
+        return out, ut, rq

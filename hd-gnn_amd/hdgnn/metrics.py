@@ -570,3 +570,121 @@ def cut_groups(merges, levels, tprime):
     for b in range(len(levels)):
         groups[b] = _components(nc, merges[b, take[b], 0], merges[b, take[b], 1])
     return groups
+
+
+# ---------------------------------------------------------------------------------------
+# Refinement: best-move sweeps on the correlation-clustering objective from any starting
+# partition, as hdg_refine runs them on the device (include/hdgnn.h, HDG_RF_*), its host
+# restatement.
+# ---------------------------------------------------------------------------------------
+RF_SLOTS, RF_MOVES, RF_NAN = 8, 6, 7
+RF_Q_SLOTS = 4
+RF_Q_START, RF_Q_END, RF_Q_SWEEPS, RF_Q_CONVERGED = range(4)
+RF_MAX_SWEEPS = 64
+
+
+def refine_gains(probs_b, tprime, rule="mean"):
+    """One commit's scores (R,) float32 and the link bound t' -> (A int64 (Nc, Nc), no-edge
+    pairs): the fixed-point gains a_pq of include/hdgnn.h, symmetric, 0 on the diagonal and
+    for a pair that is no edge."""
+    from .data import pair_index
+    nc = _nc_of(len(probs_b))
+    I, J = pair_index(nc)
+    S = np.zeros((nc, nc), np.float32)
+    S[I, J] = np.asarray(probs_b, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if rule == "mean":
+            W = S + S.T
+        elif rule == "any":
+            W = np.maximum(S, S.T)                     # NaN when either is
+        else:
+            W = np.minimum(S, S.T)
+        W = np.where(W == 0, np.float32(0), W).astype(np.float32)       # -0 -> +0
+        none = np.isnan(W)
+        np.fill_diagonal(none, False)
+        d = np.where(none, np.float32(0), W) - np.float32(tprime)       # one float32 subtraction
+        A = np.rint(np.clip(d, np.float32(-2), np.float32(2)) * np.float32(262144)).astype(np.int64)
+    A[none] = 0
+    np.fill_diagonal(A, 0)
+    return A, int(np.count_nonzero(none)) // 2
+
+
+def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8):
+    """(B, 2, R) one-hot labels and probabilities and starting groups int (B, Nc) or None
+    (every hunk alone) -> (ut int64 (B, RF_SLOTS), groups int32 (B, Nc), rq int64
+    (B, RF_Q_SLOTS)): the host restatement of hdg_refine, definitions as in include/hdgnn.h.
+    Plain: per visit of p one np.bincount of row p of the gains over the slots, then the
+    choice among stay, the other non-empty slots and the smallest empty slot (strictly above
+    stay; the largest; a non-empty slot before the empty one, then the lowest slot)."""
+    from .data import pair_index
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    thr = np.float32(threshold)
+    with np.errstate(over="ignore"):
+        tp = thr + thr if rule == "mean" else thr
+    if not (np.isfinite(thr) and np.isfinite(tp)):
+        raise ValueError("threshold %r gives no finite link bound" % (threshold,))
+    if not 1 <= int(max_sweeps) <= RF_MAX_SWEEPS:
+        raise ValueError("max_sweeps must be in [1, %d] (got %r)" % (RF_MAX_SWEEPS, max_sweeps))
+    label = np.asarray(label_onehot)
+    probs = np.asarray(probs, np.float32)
+    B, R = probs.shape[0], probs.shape[2]
+    nc = _nc_of(R)
+    if groups is not None:
+        groups = np.asarray(groups).astype(np.int64).reshape(B, nc)
+    I, J = pair_index(nc)
+    iu, ju = np.triu_indices(nc, 1)
+    ut = np.zeros((B, RF_SLOTS), np.int64)
+    out = np.zeros((B, nc), np.int32)
+    rq = np.zeros((B, RF_Q_SLOTS), np.int64)
+    Y = np.zeros((nc, nc), bool)
+    every = np.arange(nc)
+    for b in range(B):
+        A, nans = refine_gains(probs[b, 1], tp, rule)
+        slot = every.copy()
+        if groups is not None:                     # a group sits at its smallest member
+            ok = (groups[b] >= 0) & (groups[b] < nc)
+            low = np.full(nc, nc, np.int64)
+            np.minimum.at(low, groups[b][ok], every[ok])
+            slot[ok] = low[groups[b][ok]]
+        size = np.bincount(slot, minlength=nc)
+        q0 = int(A[iu, ju][slot[iu] == slot[ju]].sum())
+        moves = sweeps = conv = 0
+        q1 = q0
+        while sweeps < int(max_sweeps) and not conv:
+            moved = 0
+            for p in range(nc):
+                s = np.bincount(slot, weights=A[p], minlength=nc).astype(np.int64)   # exact
+                g = int(slot[p])
+                stay, best, to = int(s[g]), None, -1
+                cand = size > 0
+                cand[g] = False
+                if cand.any():
+                    m = int(s[cand].max())
+                    if m > stay:
+                        best, to = m, int(np.flatnonzero(cand & (s == m))[0])
+                if size[g] > 1 and 0 > stay and (best is None or 0 > best):
+                    best, to = 0, int(np.flatnonzero(size == 0)[0])
+                if best is not None:
+                    slot[p] = to
+                    size[g] -= 1
+                    size[to] += 1
+                    q1 += best - stay
+                    moved += 1
+            sweeps += 1
+            moves += moved
+            conv = int(moved == 0)
+        low = np.full(nc, nc, np.int64)
+        np.minimum.at(low, slot, every)
+        lab = low[slot]                            # every hunk's smallest group member
+        g = (np.cumsum(lab == every) - 1)[lab].astype(np.int32)
+        Y[I, J] = label[b, 1] > label[b, 0]
+        ylink = Y[iu, ju] | Y[ju, iu]
+        t = _components(nc, iu[ylink], ju[ylink])
+        sp, st = g[iu] == g[ju], t[iu] == t[ju]
+        out[b] = g
+        ut[b] = (int(g.max()) + 1, int(t.max()) + 1, np.count_nonzero(sp & st),
+                 np.count_nonzero(sp & ~st), np.count_nonzero(~sp & st),
+                 np.count_nonzero(~sp & ~st), moves, nans)
+        rq[b] = (q0, q1, sweeps, conv)
+    return ut, out, rq

@@ -599,7 +599,7 @@ class graph2graph(object):
         return scores, table
 
     # ------------------------------------------------------------------ untangle
-    def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single"):
+    def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single", refine=0):
         """Untangle the commits of the test (or train) split with the trained classifier: per
         batch Engine.forward then Engine.untangle (hdg_untangle), so only each commit's hunk
         group ids and its integer row (include/hdgnn.h, HDG_UT_*) come to the host, never the
@@ -611,20 +611,27 @@ class graph2graph(object):
         method "complete" | "average": the groups are the cut at `threshold` of each commit's
         merge tree under that linkage instead (Engine.agglomerate then Engine.cut: hdg_cut's
         row, whose slot 6 holds the merges done, not the linked pairs); "single" is
-        hdg_untangle, the link graph's components."""
+        hdg_untangle, the link graph's components.
+        refine > 0: the groups of either path go through Engine.refine (hdg_refine: at most
+        `refine` best-move sweeps at the same threshold and rule); the refined groups and
+        table (slot 6: the moves made) are what is returned and saved, and
+        untangle_refine<Ne>.npy holds each commit's objective row (HDG_RF_Q_*)."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
         if method not in _lib.AG_METHODS:
             raise ValueError("method must be one of %s (got %r)"
                              % (", ".join(_lib.AG_METHODS), method))
+        if not (isinstance(refine, int) and 0 <= refine <= _lib.RF_MAX_SWEEPS):
+            raise ValueError("refine must be an int in [0, %d] (got %r)"
+                             % (_lib.RF_MAX_SWEEPS, refine))
         _, _, train, test, maps = self._compact()
         if self.load(self.checkpoint_dir):
             print(" [*] Load SUCCESS")
         else:
             print(" [!] Load failed...")
         eng = self.engine
-        rows, ids = [], []
+        rows, ids, qs = [], [], []
         for db in self._device_batches(train if part == "train" else test, maps):
             eng.forward(db)
             if method == "single":
@@ -632,6 +639,9 @@ class graph2graph(object):
             else:
                 m, lv, cv, _, lk = eng.agglomerate(db, rule=rule, method=method)
                 g, ut = eng.cut(m, lv, cv, lk, threshold=threshold, rule=rule)
+            if refine:
+                g, ut, rq = eng.refine(db, g, threshold=threshold, rule=rule, max_sweeps=refine)
+                qs.append(rq)
             ids.append(g)
             rows.append(ut)
         nb, lb = len(rows), self.local_batch
@@ -644,6 +654,13 @@ class graph2graph(object):
             table = table.transpose(1, 0, 2, 3)
             groups = self._gather(groups).reshape(self.world, nb, lb, self.Nc)
             groups = groups.transpose(1, 0, 2, 3)
+        if refine:
+            qrows = (torch.stack(qs).cpu().numpy() if nb
+                     else np.zeros((0, lb, _lib.RF_Q_SLOTS), np.int64))
+            if self.world > 1 and nb:
+                qrows = self._gather(qrows).reshape(self.world, nb, lb, _lib.RF_Q_SLOTS)
+                qrows = qrows.transpose(1, 0, 2, 3)
+            qrows = np.ascontiguousarray(qrows.reshape(-1, _lib.RF_Q_SLOTS)).astype(np.int64)
         table = np.ascontiguousarray(table.reshape(-1, _lib.UT_SLOTS)).astype(np.int64)
         groups = np.ascontiguousarray(groups.reshape(-1, self.Nc)).astype(np.int32)
         scores = metrics.scores_from_untangle(table)
@@ -655,6 +672,13 @@ class graph2graph(object):
             print('untangle rule: %s, threshold %s' % (rule, threshold))
             if method != "single":
                 print('untangle method: %s' % method)
+            if refine:
+                np.save(step_dir + 'untangle_refine' + str(self.Ne) + '.npy', qrows)
+                print('untangle refine: %d sweeps at most, %d moves, %d of %d commits converged'
+                      % (refine, int(table[:, _lib.RF_MOVES].sum()),
+                         int(qrows[:, _lib.RF_Q_CONVERGED].sum()), len(qrows)))
+                print('untangle refine objective: %d -> %d'
+                      % (int(qrows[:, _lib.RF_Q_START].sum()), int(qrows[:, _lib.RF_Q_END].sum())))
             for name in ("rand", "precision", "recall", "f1"):
                 print('untangle %s: %s (per-commit mean %s)' % (name, scores[name],
                                                                 scores[name + "_mean"]))

@@ -16,6 +16,8 @@ MI355X instead of a TF1 session.
     python hd-gnn_amd/main.py --Type calibrate --link-method average
     python hd-gnn_amd/main.py --Type untangle --link-threshold auto --link-method complete
                                                # groups from complete / average linkage trees
+    python hd-gnn_amd/main.py --Type untangle --link-method average --link-refine 8
+                                               # ... then up to 8 best-move sweeps over them
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -51,7 +53,10 @@ def _variant(argv):
     --link-threshold auto: the threshold with the best pooled --link-score f1|rand (default
     f1) on the train split, from the commits' merge trees (hdg_linkage), which --Type
     calibrate computes alone; --link-method single|complete|average (default single: the link
-    graph's components): the linkage whose merge tree both cut (hdg_agglomerate, hdg_cut)."""
+    graph's components): the linkage whose merge tree both cut (hdg_agglomerate, hdg_cut);
+    --link-refine N (default 0: none): --Type untangle passes its groups through at most N
+    best-move sweeps (hdg_refine) at the same threshold and rule -- with --link-threshold auto
+    the one calibrated for the tree; --Type calibrate does not look at it."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
@@ -59,6 +64,7 @@ def _variant(argv):
     p.add_argument('--link-rule', default='mean', choices=('mean', 'any', 'both'))
     p.add_argument('--link-score', default='f1', choices=('f1', 'rand'))
     p.add_argument('--link-method', default='single', choices=('single', 'complete', 'average'))
+    p.add_argument('--link-refine', type=int, default=0)
     a, rest = p.parse_known_args(argv)
     return a, rest
 
@@ -137,7 +143,9 @@ def main(argv=None, model_cls=None):
             if threshold == 'auto':
                 threshold = model.calibrate(args, part="train", rule=extra.link_rule,
                                             score=extra.link_score, **how)[0]
-            model.untangle(args, threshold=threshold, rule=extra.link_rule, **how)
+            # without refinement the call is the one it always was
+            more = {'refine': extra.link_refine} if extra.link_refine else {}
+            model.untangle(args, threshold=threshold, rule=extra.link_rule, **how, **more)
         if args.Type == 'calibrate':  # not in the reference: the best link threshold, on the device
             model.calibrate(args, part="train", rule=extra.link_rule, score=extra.link_score,
                             **how)

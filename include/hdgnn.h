@@ -485,6 +485,82 @@ int    hdg_cut(const hdg_shape* shape, const int32_t* merges, const float* level
                void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * On-device refinement (csrc/refine.hip): every decode above is greedy -- a merge is never
+ * undone, so a wrong pair with the highest score of a commit is merged first by every tree
+ * and no threshold repairs it.  hdg_refine is local search on the objective the linkages
+ * approximate (correlation clustering: the sum of w_pq - t' over the pairs kept in one
+ * group), from any starting partition: best-move sweeps over the hunks.  Device and host
+ * (hdgnn.metrics.refine) agree integer for integer.
+ *
+ *   weight   w of the unordered pair {p, q} under `rule`, and the pairs that are no edge:
+ *            exactly hdg_linkage's (they count in HDG_RF_NAN as in HDG_LK_NAN)
+ *   bound    t' as hdg_untangle and hdg_cut form it, once on the host:
+ *            fl32(threshold + threshold) under MEAN, threshold otherwise; it must be finite
+ *   gain     a_pq = a_qp, fixed point: d = fl32(w - t'), one fp32 subtraction, and
+ *            a = (int32) rintf(fminf(fmaxf(d, -2.f), 2.f) * 262144.f).  The scale is a power of
+ *            two, so only rintf (ties to even) rounds.  A pair that is no edge has a = 0, and
+ *            so has the diagonal.  |a| <= 2^19, so a sum over at most 2047 partners stays
+ *            below 2^31: node sums are int32, totals int64, and every result is independent
+ *            of the order of summation.  For probabilities the clamp never binds under any
+ *            rule; pairs within 2^-19 of t' are neutral
+ *   start    with groups_in NULL every hunk starts alone; otherwise hunks with the same id in
+ *            [0, nc) start together and a hunk whose id is outside [0, nc) starts alone (no
+ *            id is used as an index before it is range-checked).  Groups live in slots
+ *            0 .. nc-1; a starting group sits in the slot of its smallest member, so the
+ *            numbering of the input does not matter
+ *   Q        the sum of a_pq over the pairs p < q in the same slot
+ *   sweep    visits p = 0, 1, .., nc-1 in that order, each visit seeing the moves of the
+ *            earlier visits of the same sweep.  For p in slot g and any slot h, S[h] is the
+ *            sum of a_pq over the q != p in slot h.  The candidates: stay, at S[g]; every
+ *            other non-empty slot h, at S[h]; if p is not alone in g, the smallest empty slot,
+ *            at 0.  p moves only to a candidate whose value is strictly above S[g], and to the
+ *            largest such value; among equal non-empty slots the lowest slot number wins, and
+ *            a non-empty slot beats the empty one at equal value
+ *   stop     after the first sweep without a move, or after max_sweeps sweeps, max_sweeps in
+ *            [1, HDG_RF_MAX_SWEEPS].  Every move raises Q by at least 1, so the process ends
+ *            without the cap; the cap bounds the kernel
+ *   groups   [batch][nc] i32, hdg_untangle's dense ids ordered by each group's smallest
+ *            member; may be the same array as groups_in
+ *   ut       [batch][HDG_RF_SLOTS] u64: slots 0 .. 5 are HDG_UT_GROUPS .. HDG_UT_DD of the final
+ *            partition against the true groups from batch->ybits (true groups as
+ *            hdg_untangle's), then HDG_RF_MOVES and HDG_RF_NAN
+ *   rq       [batch][HDG_RF_Q_SLOTS] i64: Q at the start, Q at the end, the sweeps run (the
+ *            final sweep without a move counts), and 1 if the last sweep made no move, else 0
+ *   workspace  hdg_refine_workspace_bytes(shape, flags) bytes (per commit nc * nc gains and
+ *            one count per tile pair), 8-byte aligned; its content before the call does not
+ *            matter
+ * Every slot of every output is written by the call.  Two launches on `stream`: k_rf_weights
+ * (one block per 64 x 64 tile pair of a commit, hdg_agglomerate's staging) writes the gains as
+ * a full nc x nc int32 matrix, both triangles, into the commit's region of the workspace;
+ * k_rf_sweep, one block per commit, keeps slots, sizes and the per-slot sums in LDS and reads
+ * row p of the matrix one step ahead: per step an int32 LDS atomic add per hunk, a block
+ * arg-max under the tie rules above, and one move.  The matrix has one home, the workspace,
+ * and no flag is defined.  No host synchronisation, no block waits for another, no float
+ * atomics: the same bits on every run.  The sweep loop is bounded by max_sweeps, the step
+ * loop by nc and every inner loop by nc.  Only shape->batch, shape->nc and batch->ybits are
+ * read.  HDG_EINVAL (message in hdg_last_error) for what hdg_untangle rejects, a NULL groups,
+ * ut, rq or workspace, a workspace that is not 8-byte aligned, max_sweeps out of range, any
+ * flag bit, or a threshold or t' that is not finite; nothing is launched then.            */
+#define HDG_RF_SLOTS 8
+#define HDG_RF_MOVES 6         /* moves made                                               */
+#define HDG_RF_NAN 7           /* unordered pairs that are no edge: HDG_LK_NAN's count      */
+#define HDG_RF_Q_SLOTS 4
+#define HDG_RF_Q_START 0       /* Q of the starting partition                              */
+#define HDG_RF_Q_END 1         /* Q of the final partition                                 */
+#define HDG_RF_Q_SWEEPS 2      /* sweeps run                                               */
+#define HDG_RF_Q_CONVERGED 3   /* 1: the last sweep made no move                           */
+#define HDG_RF_MAX_SWEEPS 64
+
+size_t hdg_refine_workspace_bytes(const hdg_shape* shape, int32_t flags);   /* 0 on a shape error */
+int    hdg_refine(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                  float threshold, int32_t rule, int32_t max_sweeps, int32_t flags,
+                  const int32_t* groups_in /* [batch][nc] or NULL */,
+                  int32_t* groups          /* [batch][nc] */,
+                  uint64_t* ut             /* [batch][HDG_RF_SLOTS] */,
+                  int64_t* rq              /* [batch][HDG_RF_Q_SLOTS] */,
+                  void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
  *
  * Instead of an RCCL call between hdg_fwd_bwd and hdg_adam_tf, the step's reduction
