@@ -4,10 +4,10 @@
 // slot.
 //
 // hdg_agglomerate, three launches, neither waits for another block:
-//   k_ag_weights  grid (tile pairs, B), 512 threads: k_ut_link's staging of the I x J segment
-//                 of the scores and its mirror through two 64 x 65 LDS tiles, one tile pair
-//                 per block.  Every p < q of the tile gets its weight under the rule
-//                 (ut_weight, the statement k_lk_forest uses; NaN stands for "no edge") at
+//   k_ag_weights  grid (ut_tiles(nc), B), 512 threads: the staging of the I x J segment of the
+//                 scores and its mirror through two 64 x 65 LDS tiles (ut_stage), one tile
+//                 pair per block.  Every p < q of the tile (ut_visit) gets its weight under the
+//                 rule (ut_weight, the statement k_lk_forest uses; NaN stands for "no edge") at
 //                 its place in the commit's region of the workspace: the upper triangle
 //                 packed by rows, (x, y), x < y, at x nc - x (x + 1) / 2 + y - x - 1, so the
 //                 partners c > x of a row are contiguous.  The block's count of pairs that
@@ -27,7 +27,8 @@
 //   k_ag_close    grid B, 1024 threads: the merges in array order through treeclose.h, the
 //                 closing phase k_lk_close runs -> curve, tgroups, lk.
 // hdg_cut, one launch: k_cut, grid B, unites the merges above the bound in unionfind.h's
-// forest and labels it with ut_label, as k_ut_close does.
+// forest and labels it with ut_label; its table comes off the curve, slot for slot
+// hdg_untangle's (the static_asserts of unionfind.h).
 // Integer and bit results only; the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,15 +50,11 @@ static_assert(AG_LDS_N >= 160, "every fused-path shape keeps its matrix in LDS")
 static_assert(AG_LDS_TRI * 4 + AG_LDS_N * 20 + 1024 <= 160 * 1024, "k_ag_merge's LDS budget");
 static_assert(UT_MAXN * (UT_MAXN - 1) / 2 < (1 << 22), "the packed index fits 32 bits");
 
-__host__ __device__ inline int ag_tiles(const int nc) {
-  const int T = (nc + UT_T - 1) / UT_T;
-  return T * (T + 1) / 2;
-}
 __host__ __device__ inline uint32_t ag_tri(const int nc) {
   return (uint32_t)nc * (uint32_t)(nc - 1) / 2u;
 }
-// workspace, in 4-byte words per commit: the packed triangle, then ag_tiles(nc) no-edge
-// counts; nc (nc + 1) / 2 >= ag_tiles(nc) words are left after the triangle
+// workspace, in 4-byte words per commit: the packed triangle, then ut_tiles(nc) no-edge
+// counts; nc (nc + 1) / 2 >= ut_tiles(nc) words are left after the triangle
 __host__ __device__ inline size_t ag_commit_words(const int nc) { return (size_t)nc * (size_t)nc; }
 __device__ __forceinline__ uint32_t ag_idx(const int x, const int y, const int nc) {   // x < y
   return (uint32_t)x * (uint32_t)nc - (uint32_t)x * (uint32_t)(x + 1) / 2u + (uint32_t)(y - x - 1);
@@ -70,52 +67,27 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_ag_weights(const float* __restri
   __shared__ float sb[UT_T * UT_LD];       // sb[c][a] = s(64 J + c, 64 I + a)
   __shared__ uint32_t red[UT_LINK_WAVES];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.y;
-  const int n1 = nc - 1;
-  const size_t ncr = (size_t)nc * n1;
-  const float* s = probs + (size_t)b * 2 * ncr + ncr;     // channel 1
-  const int T = (nc + UT_T - 1) / UT_T;
-  int I = 0, rem = (int)blockIdx.x;        // this block's tile pair, row-major over I <= J
-  while (rem >= T - I) {
-    rem -= T - I;
-    ++I;
-  }
-  const int p0 = I * UT_T, q0 = (I + rem) * UT_T;
-  for (int idx = tid; idx < UT_T * UT_T; idx += UT_LINK_NT) {
-    const int row = idx >> 6, col = idx & 63;
-    int p = p0 + row, q = q0 + col;        // a row of the I x J segment
-    float v = 0.f;
-    if (p < nc && q < nc && p != q) v = s[(size_t)p * n1 + q - (q > p)];
-    sa[row * UT_LD + col] = v;
-    p = q0 + row, q = p0 + col;            // a row of the mirror segment
-    v = 0.f;
-    if (p < nc && q < nc && p != q) v = s[(size_t)p * n1 + q - (q > p)];
-    sb[row * UT_LD + col] = v;
-  }
+  int p0, q0;                              // this block's tile pair
+  ut_tile_pair((int)blockIdx.x, nc, p0, q0);
+  ut_stage(ut_scores(probs, b, nc), nc, p0, q0, sa, sb);
   __syncthreads();
   float* wb = ws + (size_t)b * ag_commit_words(nc);
   uint32_t nans = 0;
-  for (int idx = tid; idx < UT_T * UT_T; idx += UT_LINK_NT) {
-    const int a = idx >> 6, c = idx & 63;
-    const int p = p0 + a, q = q0 + c;
-    if (p < q && q < nc) {
-      float w;
-      if (!ut_weight(rule, sa[a * UT_LD + c], sb[c * UT_LD + a], w)) {
-        ++nans;
-        w = __uint_as_float(0x7FC00000u);
-      }
-      wb[ag_idx(p, q, nc)] = w;
-    }
-  }
-  nans = ut_wave_sum(nans);
-  if (lane == 0) red[wave] = nans;
+  ut_visit(nc, p0, q0, sa, sb,
+           [&](int, int, int, const int p, const int q, const float spq, const float sqp) {
+             float w;
+             if (!ut_weight(rule, spq, sqp, w)) {
+               ++nans;
+               w = __uint_as_float(0x7FC00000u);
+             }
+             wb[ag_idx(p, q, nc)] = w;
+           });
+  ut_count_put(red, nans);
   __syncthreads();
-  if (tid == 0) {
-    uint32_t v = 0;
-    for (int w = 0; w < UT_LINK_WAVES; ++w) v += red[w];
-    reinterpret_cast<uint32_t*>(wb)[ag_tri(nc) + blockIdx.x] = v;
-  }
+  if (threadIdx.x == 0)
+    reinterpret_cast<uint32_t*>(wb)[ag_tri(nc) + blockIdx.x] =
+        ut_count_sum<uint32_t, UT_LINK_WAVES>(red, 0);
 }
 
 // (v, i) before (ov, oi) in the order (value descending, index ascending); an index < 0 is
@@ -294,7 +266,7 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_ag_close(const float* __restric
   __shared__ uint32_t nxt[2 * UT_MAXN];
   __shared__ uint32_t cnt[UT_CLOSE_WAVES];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x;
   const int n1 = nc - 1;
   uint32_t have = 0;
@@ -305,16 +277,14 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_ag_close(const float* __restric
     mq[k] = real ? (uint32_t)q : 0u;
     have += real;
   }
-  have = ut_wave_sum(have);
-  if (lane == 0) cnt[wave] = have;
+  ut_count_put(cnt, have);
   __syncthreads();
-  int M = 0;
-  for (int w = 0; w < UT_CLOSE_WAVES; ++w) M += (int)cnt[w];     // the real rows are a prefix
+  const int M = ut_count_sum<int, UT_CLOSE_WAVES>(cnt, 0);       // the real rows are a prefix
   u64 nans = 0;
   if (tid == 0) {
     const uint32_t* c = reinterpret_cast<const uint32_t*>(ws + (size_t)b * ag_commit_words(nc)) +
                         ag_tri(nc);
-    const int tiles = ag_tiles(nc);
+    const int tiles = ut_tiles(nc);
     for (int f = 0; f < tiles; ++f) nans += c[f];
   }
   tc_close(par, comp, nxt,
@@ -322,7 +292,7 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_ag_close(const float* __restric
              x = mp[k];
              y = mq[k];
            },
-           M, nans, ybits + (size_t)b * nc * ((nc + 31) >> 5), curve + (size_t)b * n1 * 2,
+           M, nans, ut_label_rows(ybits, b, nc), curve + (size_t)b * n1 * 2,
            tgroups ? tgroups + (size_t)b * nc : nullptr, lk + (size_t)b * HDG_LK_SLOTS, nc);
 }
 
@@ -338,7 +308,7 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_cut(const int32_t* __restrict__
   __shared__ uint32_t wsum[UT_CLOSE_WAVES];
   __shared__ uint32_t red[UT_CLOSE_WAVES];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x;
   const int n1 = nc - 1;
   for (int i = tid; i < nc; i += UT_CLOSE_NT) par[i] = (uint32_t)i;
@@ -352,14 +322,12 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_cut(const int32_t* __restrict__
       ++done;
     }
   }
-  done = ut_wave_sum(done);
-  if (lane == 0) red[wave] = done;
+  ut_count_put(red, done);
   __syncthreads();
   const uint32_t G = ut_label(par, rnk, g, wsum, nc);
   for (int i = tid; i < nc; i += UT_CLOSE_NT) groups[(size_t)b * nc + i] = (int32_t)g[i];
   if (ut && tid == 0) {
-    uint32_t k = 0;
-    for (int w = 0; w < UT_CLOSE_WAVES; ++w) k += red[w];
+    uint32_t k = ut_count_sum<uint32_t, UT_CLOSE_WAVES>(red, 0);
     if (k > (uint32_t)n1) k = (uint32_t)n1;
     const u64 sp = k ? curve[2 * ((size_t)b * n1 + k - 1)] : 0ull;
     const u64 ss = k ? curve[2 * ((size_t)b * n1 + k - 1) + 1] : 0ull;
@@ -377,10 +345,6 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_cut(const int32_t* __restrict__
   }
 }
 
-inline bool ag_rule_ok(const int32_t rule) {
-  return rule == HDG_UT_RULE_MEAN || rule == HDG_UT_RULE_ANY || rule == HDG_UT_RULE_BOTH;
-}
-
 }  // namespace
 
 extern "C" size_t hdg_agglomerate_workspace_bytes(const hdg_shape* s, int32_t flags) {
@@ -394,9 +358,7 @@ extern "C" int hdg_agglomerate(const hdg_shape* s, const hdg_batch* bt, const fl
                                float* levels, uint32_t* curve, int32_t* tgroups, uint64_t* lk,
                                void* workspace, void* stream) {
   if (const int rc = ut_check_shape(s, "hdg_agglomerate")) return rc;
-  if (!ag_rule_ok(rule))
-    return fail(HDG_EINVAL, "hdg_agglomerate: unknown rule %d (HDG_UT_RULE_MEAN / _ANY / _BOTH)",
-                (int)rule);
+  if (const int rc = ut_check_rule(rule, "hdg_agglomerate")) return rc;
   if (method != HDG_AG_SINGLE && method != HDG_AG_COMPLETE && method != HDG_AG_AVERAGE)
     return fail(HDG_EINVAL, "hdg_agglomerate: unknown method %d (HDG_AG_SINGLE / _COMPLETE / "
                             "_AVERAGE)", (int)method);
@@ -405,48 +367,36 @@ extern "C" int hdg_agglomerate(const hdg_shape* s, const hdg_batch* bt, const fl
   if (!bt || !bt->ybits || !probs || !merges || !levels || !curve || !lk || !workspace)
     return fail(HDG_EINVAL, "hdg_agglomerate: NULL pointer (batch, batch->ybits, probs, merges, "
                             "levels, curve, lk or workspace)");
-  if ((uintptr_t)workspace & 7u)
-    return fail(HDG_EINVAL, "hdg_agglomerate: workspace must be 8-byte aligned");
+  if (const int rc = ut_check_workspace(workspace, "hdg_agglomerate")) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nc = s->nc;
-  hipLaunchKernelGGL(k_ag_weights, dim3((unsigned)ag_tiles(nc), (unsigned)s->batch),
+  hipLaunchKernelGGL(k_ag_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
                      dim3(UT_LINK_NT), 0, st, probs, (float*)workspace, nc, (int)rule);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail((int)e, "hdg_agglomerate: launch (weights): %s", hipGetErrorString(e));
+  if (const int rc = ut_launched("hdg_agglomerate", "weights")) return rc;
   if (nc <= HDG_AG_LDS_MAX_NC && !(flags & HDG_AG_FLAG_GLOBAL))
     hipLaunchKernelGGL(k_ag_merge<true>, dim3((unsigned)s->batch), dim3(AG_NT), 0, st,
                        (float*)workspace, merges, levels, nc, (int)method);
   else
     hipLaunchKernelGGL(k_ag_merge<false>, dim3((unsigned)s->batch), dim3(AG_NT), 0, st,
                        (float*)workspace, merges, levels, nc, (int)method);
-  e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail((int)e, "hdg_agglomerate: launch (merge): %s", hipGetErrorString(e));
+  if (const int rc = ut_launched("hdg_agglomerate", "merge")) return rc;
   hipLaunchKernelGGL(k_ag_close, dim3((unsigned)s->batch), dim3(UT_CLOSE_NT), 0, st,
                      (const float*)workspace, bt->ybits, (const int32_t*)merges, curve, tgroups,
                      (u64*)lk, nc);
-  e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail((int)e, "hdg_agglomerate: launch (close): %s", hipGetErrorString(e));
-  return 0;
+  return ut_launched("hdg_agglomerate", "close");
 }
 
 extern "C" int hdg_cut(const hdg_shape* s, const int32_t* merges, const float* levels,
                        const uint32_t* curve, const uint64_t* lk, float threshold, int32_t rule,
                        int32_t* groups, uint64_t* ut, void* stream) {
   if (const int rc = ut_check_shape(s, "hdg_cut")) return rc;
-  if (!ag_rule_ok(rule))
-    return fail(HDG_EINVAL, "hdg_cut: unknown rule %d (HDG_UT_RULE_MEAN / _ANY / _BOTH)", (int)rule);
+  if (const int rc = ut_check_rule(rule, "hdg_cut")) return rc;
   if (threshold != threshold) return fail(HDG_EINVAL, "hdg_cut: threshold is NaN");
   if (!merges || !levels || !groups)
     return fail(HDG_EINVAL, "hdg_cut: NULL pointer (merges, levels or groups)");
   if (ut && (!curve || !lk)) return fail(HDG_EINVAL, "hdg_cut: ut needs curve and lk");
-  volatile float two = threshold;          // fl32(threshold + threshold), once, as hdg_untangle
-  const float bound = rule == HDG_UT_RULE_MEAN ? two + two : threshold;
   hipLaunchKernelGGL(k_cut, dim3((unsigned)s->batch), dim3(UT_CLOSE_NT), 0, (hipStream_t)stream,
-                     merges, levels, curve, (const u64*)lk, bound, groups, (u64*)ut, s->nc);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, "hdg_cut: launch: %s", hipGetErrorString(e));
-  return 0;
+                     merges, levels, curve, (const u64*)lk, ut_link_bound(rule, threshold), groups,
+                     (u64*)ut, s->nc);
+  return ut_launched("hdg_cut", nullptr);
 }

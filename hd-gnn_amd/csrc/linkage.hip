@@ -11,7 +11,8 @@
 // outgoing key) can never close a cycle, whatever order the threads run in.
 //
 // Two launches, neither waits for another block:
-//   k_lk_forest  grid (ut_blocks(nc), B), 512 threads: k_ut_link's tile pairs and staging.
+//   k_lk_forest  grid (ut_blocks(nc), B), 512 threads: the tile pairs, staging and visit
+//                k_ut_link uses (ut_tile_pair, ut_stage, ut_visit), the weight by ut_weight.
 //                The block keeps a running forest of at most nc - 1 keys in LDS (the forest
 //                of a union of edge sets is the forest of the union of their forests) and,
 //                per tile pair, runs Boruvka rounds over {that forest} + {the tile's <= 4096
@@ -20,7 +21,7 @@
 //   k_lk_close   grid B, 1024 threads.  Boruvka over the keys of the commit's block forests,
 //                a bitonic sort of the M survivors (descending: Kruskal's acceptance order)
 //                -> merges, levels; then the closing phase hdg_agglomerate shares
-//                (treeclose.h): the true groups as k_ut_close builds them, the dendrogram
+//                (treeclose.h): the true groups (ut_true_groups), the dendrogram
 //                order of the hunks, the pairs each merge joins, and their inclusive scan
 //                over k, the curve.
 // Integer and bit results only; the same bits on every run.
@@ -36,7 +37,6 @@ namespace {
 using hdg::fail;
 typedef unsigned long long u64;
 
-constexpr int LK_EPT = UT_T * UT_T / UT_LINK_NT;      // tile edges per thread of k_lk_forest
 constexpr int LK_MAX_ROUNDS = 32;                     // > ceil(log2 2048) + 1: never reached
 static_assert(UT_MAXN == 2048, "the key's low word packs p * 2048 + q");
 
@@ -108,51 +108,30 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_lk_forest(const float* __restric
   __shared__ uint32_t red[UT_LINK_WAVES];
   __shared__ uint32_t count;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int blk = blockIdx.x, b = blockIdx.y;
   const int n1 = nc - 1;
-  const size_t ncr = (size_t)nc * n1;
-  const float* s = probs + (size_t)b * 2 * ncr + ncr;     // channel 1
-  const int T = (nc + UT_T - 1) / UT_T, tiles = T * (T + 1) / 2;
+  const float* s = ut_scores(probs, b, nc);
+  const int tiles = ut_tiles(nc);
 
   uint32_t nans = 0, m = 0;                // m: keys of the running forest, forest[cur]
   int cur = 0;
   for (int k = blk; k < tiles; k += nblk) {
-    int I = 0, rem = k;                    // tile pair k, row-major over I <= J
-    while (rem >= T - I) {
-      rem -= T - I;
-      ++I;
-    }
-    const int p0 = I * UT_T, q0 = (I + rem) * UT_T;
+    int p0, q0;
+    ut_tile_pair(k, nc, p0, q0);
     __syncthreads();                       // the last tile pair's rounds are over
-    for (int idx = tid; idx < UT_T * UT_T; idx += UT_LINK_NT) {
-      const int row = idx >> 6, col = idx & 63;
-      int p = p0 + row, q = q0 + col;      // a row of the I x J segment
-      float v = 0.f;
-      if (p < nc && q < nc && p != q) v = s[(size_t)p * n1 + q - (q > p)];
-      sa[row * UT_LD + col] = v;
-      p = q0 + row, q = p0 + col;          // a row of the mirror segment
-      v = 0.f;
-      if (p < nc && q < nc && p != q) v = s[(size_t)p * n1 + q - (q > p)];
-      sb[row * UT_LD + col] = v;
-    }
+    ut_stage(s, nc, p0, q0, sa, sb);
     for (int i = tid; i < nc; i += UT_LINK_NT) parent[i] = (uint32_t)i;
     if (tid == 0) count = 0u;
     __syncthreads();
-    u64 key[LK_EPT];                       // this thread's edges of the tile pair, 0 = none
-#pragma unroll
-    for (int u = 0; u < LK_EPT; ++u) {
-      const int idx = tid + u * UT_LINK_NT;
-      const int a = idx >> 6, c = idx & 63;
-      const int p = p0 + a, q = q0 + c;
-      key[u] = 0ull;
-      if (p < q && q < nc) {
-        const float spq = sa[a * UT_LD + c], sqp = sb[c * UT_LD + a];
-        float w;
-        if (!ut_weight(rule, spq, sqp, w)) ++nans;
-        else key[u] = lk_key(w, p, q);
-      }
-    }
+    u64 key[UT_VISITS] = {};               // this thread's edges of the tile pair, 0 = none
+    ut_visit(nc, p0, q0, sa, sb,
+             [&](const int u, int, int, const int p, const int q, const float spq,
+                 const float sqp) {
+               float w;
+               if (!ut_weight(rule, spq, sqp, w)) ++nans;
+               else key[u] = lk_key(w, p, q);
+             });
     const u64* old = forest[cur];
     u64* out = forest[cur ^ 1];
     uint32_t have = 0;
@@ -160,7 +139,7 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_lk_forest(const float* __restric
       lk_snapshot<UT_LINK_NT>(parent, comp, best, nc);
       __syncthreads();
 #pragma unroll
-      for (int u = 0; u < LK_EPT; ++u)     // a key inside one component stays inside it
+      for (int u = 0; u < UT_VISITS; ++u)  // a key inside one component stays inside it
         if (key[u] && !lk_offer(comp, best, key[u])) key[u] = 0ull;
       for (uint32_t i = tid; i < m; i += UT_LINK_NT) lk_offer(comp, best, old[i]);
       __syncthreads();
@@ -178,14 +157,9 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_lk_forest(const float* __restric
   u64* wb = ws + (size_t)b * lk_commit_words(nc, nblk);
   const u64* f = forest[cur];
   for (int i = tid; i < n1; i += UT_LINK_NT) wb[(size_t)blk * n1 + i] = (uint32_t)i < m ? f[i] : 0ull;
-  nans = ut_wave_sum(nans);
-  if (lane == 0) red[wave] = nans;
+  ut_count_put(red, nans);
   __syncthreads();
-  if (tid == 0) {
-    u64 v = 0;
-    for (int w = 0; w < UT_LINK_WAVES; ++w) v += red[w];
-    wb[(size_t)nblk * n1 + blk] = v;
-  }
+  if (tid == 0) wb[(size_t)nblk * n1 + blk] = ut_count_sum<u64, UT_LINK_WAVES>(red, 0);
 }
 
 __global__ __launch_bounds__(UT_CLOSE_NT) void k_lk_close(const u64* __restrict__ ws,
@@ -267,7 +241,7 @@ __global__ __launch_bounds__(UT_CLOSE_NT) void k_lk_close(const u64* __restrict_
              x = lk_p(key);
              y = lk_q(key);
            },
-           M, nans, ybits + (size_t)b * nc * ((nc + 31) >> 5), curve + (size_t)b * n1 * 2,
+           M, nans, ut_label_rows(ybits, b, nc), curve + (size_t)b * n1 * 2,
            tgroups ? tgroups + (size_t)b * nc : nullptr, lk + (size_t)b * HDG_LK_SLOTS, nc);
 }
 
@@ -282,24 +256,18 @@ extern "C" int hdg_linkage(const hdg_shape* s, const hdg_batch* bt, const float*
                            int32_t rule, int32_t* merges, float* levels, uint32_t* curve,
                            int32_t* tgroups, uint64_t* lk, void* workspace, void* stream) {
   if (const int rc = ut_check_shape(s, "hdg_linkage")) return rc;
-  if (rule != HDG_UT_RULE_MEAN && rule != HDG_UT_RULE_ANY && rule != HDG_UT_RULE_BOTH)
-    return fail(HDG_EINVAL, "hdg_linkage: unknown rule %d (HDG_UT_RULE_MEAN / _ANY / _BOTH)",
-                (int)rule);
+  if (const int rc = ut_check_rule(rule, "hdg_linkage")) return rc;
   if (!bt || !bt->ybits || !probs || !merges || !levels || !curve || !lk || !workspace)
     return fail(HDG_EINVAL, "hdg_linkage: NULL pointer (batch, batch->ybits, probs, merges, "
                             "levels, curve, lk or workspace)");
-  if ((uintptr_t)workspace & 7u)
-    return fail(HDG_EINVAL, "hdg_linkage: workspace must be 8-byte aligned");
+  if (const int rc = ut_check_workspace(workspace, "hdg_linkage")) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nblk = ut_blocks(s->nc);
   hipLaunchKernelGGL(k_lk_forest, dim3((unsigned)nblk, (unsigned)s->batch), dim3(UT_LINK_NT), 0, st,
                      probs, (u64*)workspace, s->nc, nblk, (int)rule);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, "hdg_linkage: launch (forest): %s", hipGetErrorString(e));
+  if (const int rc = ut_launched("hdg_linkage", "forest")) return rc;
   hipLaunchKernelGGL(k_lk_close, dim3((unsigned)s->batch), dim3(UT_CLOSE_NT), 0, st,
                      (const u64*)workspace, bt->ybits, merges, levels, curve, tgroups,
                      (u64*)lk, s->nc, nblk);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, "hdg_linkage: launch (close): %s", hipGetErrorString(e));
-  return 0;
+  return ut_launched("hdg_linkage", "close");
 }

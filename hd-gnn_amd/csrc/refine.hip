@@ -4,10 +4,11 @@
 // are the header's; every result is an integer and independent of summation order.
 //
 // Two launches, neither waits for another block:
-//   k_rf_weights  grid (tile pairs, B), 512 threads: k_ag_weights' staging of the I x J segment
-//                 of the scores and its mirror through two 64 x 65 LDS tiles, one tile pair
-//                 per block.  Every p < q of the tile gets its weight (ut_weight) and from it
-//                 the gain a_pq = rint(clamp(w - t') * 2^18), 0 for a pair that is no edge.
+//   k_rf_weights  grid (ut_tiles(nc), B), 512 threads: the staging of the I x J segment of the
+//                 scores and its mirror through two 64 x 65 LDS tiles (ut_stage), one tile pair
+//                 per block.  Every p < q of the tile (ut_visit) gets its weight (ut_weight)
+//                 and from it the gain a_pq = rint(clamp(w - t') * 2^18), 0 for a pair that is
+//                 no edge.
 //                 The commit's region of the workspace holds the full nc x nc int32 matrix,
 //                 written at (p, q) by rows of the segment and, through the second LDS tile,
 //                 at (q, p) by rows of the mirror: both stores are row-coalesced, and the
@@ -26,8 +27,9 @@
 //                 owner of p and thread 0 apply it.  Two barriers per step; what a step
 //                 writes is read only after the next step's first barrier.  The sweep loop is
 //                 bounded by max_sweeps, the step loop by nc, every inner loop by nc.  Then
-//                 the final slots and the label graph are labelled (ut_label), the pairs
-//                 counted as k_ut_close counts them, and groups, ut and rq written.
+//                 the final slots and the label graph are labelled (ut_label, ut_true_groups),
+//                 the pairs counted (ut_pair_counts, ut_pair_table), and groups, ut and rq
+//                 written.
 // Integer results only; the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -48,14 +50,10 @@ static_assert(RF_NT * UT_PER == UT_MAXN, "a thread owns UT_PER hunks and slots")
 static_assert((UT_MAXN - 1) * (1ll << 19) < (1ll << 31), "a node sum fits int32");
 static_assert(UT_MAXN <= 2048, "the key's tie field holds two ranges of 2048 slots");
 
-__host__ __device__ inline int rf_tiles(const int nc) {
-  const int T = (nc + UT_T - 1) / UT_T;
-  return T * (T + 1) / 2;
-}
-// workspace, in 4-byte words per commit: the nc x nc matrix of gains, then rf_tiles(nc)
+// workspace, in 4-byte words per commit: the nc x nc matrix of gains, then ut_tiles(nc)
 // no-edge counts, rounded up to an even number of words
 __host__ __device__ inline size_t rf_commit_words(const int nc) {
-  return ((size_t)nc * (size_t)nc + (size_t)rf_tiles(nc) + 1) & ~(size_t)1;
+  return ((size_t)nc * (size_t)nc + (size_t)ut_tiles(nc) + 1) & ~(size_t)1;
 }
 
 // the fixed-point gain of a pair of weight w against the link bound tp (finite)
@@ -71,60 +69,35 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_rf_weights(const float* __restri
   __shared__ float sb[UT_T * UT_LD];       // sb[c][a] = s(64 J + c, 64 I + a), then a's bits
   __shared__ uint32_t red[UT_LINK_WAVES];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.y;
-  const int n1 = nc - 1;
-  const size_t ncr = (size_t)nc * n1;
-  const float* s = probs + (size_t)b * 2 * ncr + ncr;     // channel 1
-  const int T = (nc + UT_T - 1) / UT_T;
-  int I = 0, rem = (int)blockIdx.x;        // this block's tile pair, row-major over I <= J
-  while (rem >= T - I) {
-    rem -= T - I;
-    ++I;
-  }
-  const int p0 = I * UT_T, q0 = (I + rem) * UT_T;
-  for (int idx = tid; idx < UT_T * UT_T; idx += UT_LINK_NT) {
-    const int row = idx >> 6, col = idx & 63;
-    int p = p0 + row, q = q0 + col;        // a row of the I x J segment
-    float v = 0.f;
-    if (p < nc && q < nc && p != q) v = s[(size_t)p * n1 + q - (q > p)];
-    sa[row * UT_LD + col] = v;
-    p = q0 + row, q = p0 + col;            // a row of the mirror segment
-    v = 0.f;
-    if (p < nc && q < nc && p != q) v = s[(size_t)p * n1 + q - (q > p)];
-    sb[row * UT_LD + col] = v;
-  }
+  int p0, q0;                              // this block's tile pair
+  ut_tile_pair((int)blockIdx.x, nc, p0, q0);
+  ut_stage(ut_scores(probs, b, nc), nc, p0, q0, sa, sb);
   __syncthreads();
   int32_t* wb = ws + (size_t)b * rf_commit_words(nc);
   uint32_t nans = 0;
-  for (int idx = tid; idx < UT_T * UT_T; idx += UT_LINK_NT) {
-    const int a = idx >> 6, c = idx & 63;
-    const int p = p0 + a, q = q0 + c;
-    if (p < q && q < nc) {                 // only this thread reads or writes sb[c][a]
-      float w;
-      int32_t g = 0;
-      if (ut_weight(rule, sa[a * UT_LD + c], sb[c * UT_LD + a], w)) g = rf_gain(w, tp);
-      else ++nans;
-      wb[(size_t)p * nc + q] = g;
-      sb[c * UT_LD + a] = __int_as_float(g);
-    } else if (p == q && q < nc) {
-      wb[(size_t)p * nc + q] = 0;
-    }
-  }
+  ut_visit(nc, p0, q0, sa, sb,             // only this thread reads or writes sb[c][a]
+           [&](int, const int a, const int c, const int p, const int q, const float spq,
+               const float sqp) {
+             float w;
+             int32_t g = 0;
+             if (ut_weight(rule, spq, sqp, w)) g = rf_gain(w, tp);
+             else ++nans;
+             wb[(size_t)p * nc + q] = g;
+             sb[c * UT_LD + a] = __int_as_float(g);
+           });
+  if (p0 == q0 && tid < UT_T && p0 + tid < nc) wb[(size_t)(p0 + tid) * (nc + 1)] = 0;     // (p, p)
   __syncthreads();
-  for (int idx = tid; idx < UT_T * UT_T; idx += UT_LINK_NT) {
-    const int c = idx >> 6, a = idx & 63;  // a row of the mirror: (q, p) for the p < q above
-    const int p = p0 + a, q = q0 + c;
-    if (p < q && q < nc) wb[(size_t)q * nc + p] = __float_as_int(sb[c * UT_LD + a]);
-  }
-  nans = ut_wave_sum(nans);
-  if (lane == 0) red[wave] = nans;
+  ut_visit<true>(nc, p0, q0, sa, sb,       // by rows of the mirror: (q, p) for the p < q above
+                 [&](int, int, int, const int p, const int q, float, const float gqp) {
+                   wb[(size_t)q * nc + p] = __float_as_int(gqp);
+                 });
+  ut_count_put(red, nans);
   __syncthreads();
-  if (tid == 0) {
-    uint32_t v = 0;
-    for (int w = 0; w < UT_LINK_WAVES; ++w) v += red[w];
-    reinterpret_cast<uint32_t*>(wb)[(size_t)nc * nc + blockIdx.x] = v;
-  }
+  if (tid == 0)
+    reinterpret_cast<uint32_t*>(wb)[(size_t)nc * nc + blockIdx.x] =
+        ut_count_sum<uint32_t, UT_LINK_WAVES>(red, 0);
 }
 
 // a candidate of a step as one key: the larger key wins.  Value, then a non-empty slot
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
   __shared__ u64 wkey[RF_WAVES];
   __shared__ long long wq[RF_WAVES];
   __shared__ uint32_t wsum[UT_CLOSE_WAVES];
-  __shared__ uint32_t red[UT_CLOSE_WAVES][3];
+  __shared__ uint32_t red[UT_CLOSE_WAVES * 3];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
@@ -319,65 +292,19 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
   __syncthreads();
   const uint32_t G = ut_label(par, rnk, g, wsum, nc);
 
-  // ---- true groups: the set bits of the commit's label rows ---------------------------------
-  for (int i = tid; i < nc; i += RF_NT) par[i] = (uint32_t)i;
-  __syncthreads();
-  ut_unite_labels(par, ybits + (size_t)b * nc * ((nc + 31) >> 5), nc);
-  __syncthreads();
-  const uint32_t TG = ut_label(par, rnk, t, wsum, nc);
-
-  // ---- pair counts: this thread's q against every p < q, as k_ut_close ----------------------
-  uint32_t gq[UT_PER], tq[UT_PER];
-#pragma unroll
-  for (int u = 0; u < UT_PER; ++u) {
-    const int q = tid + u * RF_NT;
-    gq[u] = q < nc ? g[q] : 0u;
-    tq[u] = q < nc ? t[q] : 0u;
-  }
-  uint32_t same_p = 0, same_t = 0, ss = 0;
-  for (int p = 0; p < nc - 1; ++p) {
-    const uint32_t gp = g[p], tp = t[p];
-#pragma unroll
-    for (int u = 0; u < UT_PER; ++u) {
-      const int q = tid + u * RF_NT;
-      if (q > p && q < nc) {
-        const uint32_t ep = gq[u] == gp, et = tq[u] == tp;
-        same_p += ep;
-        same_t += et;
-        ss += ep & et;
-      }
-    }
-  }
-  same_p = ut_wave_sum(same_p);
-  same_t = ut_wave_sum(same_t);
-  ss = ut_wave_sum(ss);
-  if (lane == 0) {
-    red[wave][0] = same_p;
-    red[wave][1] = same_t;
-    red[wave][2] = ss;
-  }
+  const uint32_t TG = ut_true_groups(par, rnk, t, wsum, ut_label_rows(ybits, b, nc), nc);
+  ut_pair_counts(g, t, red, nc);
 
   // ---- outputs ------------------------------------------------------------------------------
   for (int i = tid; i < nc; i += RF_NT) groups[(size_t)b * nc + i] = (int32_t)g[i];
   __syncthreads();
   if (tid == 0) {
-    u64 sp = 0, st = 0, s2 = 0, nans = 0;
-    for (int w = 0; w < UT_CLOSE_WAVES; ++w) {
-      sp += red[w][0];
-      st += red[w][1];
-      s2 += red[w][2];
-    }
-    const uint32_t* cnt = reinterpret_cast<const uint32_t*>(wb) + (size_t)nc * nc;
-    const int tiles = rf_tiles(nc);
-    for (int f = 0; f < tiles; ++f) nans += cnt[f];
-    const u64 all = (u64)nc * (u64)(nc - 1) / 2ull;
     u64* row = ut + (size_t)b * HDG_RF_SLOTS;
-    row[HDG_UT_GROUPS] = G;
-    row[HDG_UT_TGROUPS] = TG;
-    row[HDG_UT_SS] = s2;
-    row[HDG_UT_SD] = sp - s2;
-    row[HDG_UT_DS] = st - s2;
-    row[HDG_UT_DD] = all - sp - st + s2;
+    ut_pair_table(red, G, TG, nc, row);
+    u64 nans = 0;
+    const uint32_t* cnt = reinterpret_cast<const uint32_t*>(wb) + (size_t)nc * nc;
+    const int tiles = ut_tiles(nc);
+    for (int f = 0; f < tiles; ++f) nans += cnt[f];
     row[HDG_RF_MOVES] = moves;
     row[HDG_RF_NAN] = nans;
     long long* qrow = rq + (size_t)b * HDG_RF_Q_SLOTS;
@@ -401,34 +328,26 @@ extern "C" int hdg_refine(const hdg_shape* s, const hdg_batch* bt, const float* 
                           const int32_t* groups_in, int32_t* groups, uint64_t* ut, int64_t* rq,
                           void* workspace, void* stream) {
   if (const int rc = ut_check_shape(s, "hdg_refine")) return rc;
-  if (rule != HDG_UT_RULE_MEAN && rule != HDG_UT_RULE_ANY && rule != HDG_UT_RULE_BOTH)
-    return fail(HDG_EINVAL, "hdg_refine: unknown rule %d (HDG_UT_RULE_MEAN / _ANY / _BOTH)",
-                (int)rule);
+  if (const int rc = ut_check_rule(rule, "hdg_refine")) return rc;
   if (max_sweeps < 1 || max_sweeps > HDG_RF_MAX_SWEEPS)
     return fail(HDG_EINVAL, "hdg_refine: max_sweeps must be in [1, %d] (got %d)",
                 HDG_RF_MAX_SWEEPS, (int)max_sweeps);
   if (flags != 0) return fail(HDG_EINVAL, "hdg_refine: unknown flag bits 0x%x", (unsigned)flags);
-  volatile float two = threshold;          // fl32(threshold + threshold), once, as hdg_untangle
-  const float tp = rule == HDG_UT_RULE_MEAN ? two + two : threshold;
+  const float tp = ut_link_bound(rule, threshold);
   if (!std::isfinite(threshold) || !std::isfinite(tp))
     return fail(HDG_EINVAL, "hdg_refine: threshold %g gives no finite link bound",
                 (double)threshold);
   if (!bt || !bt->ybits || !probs || !groups || !ut || !rq || !workspace)
     return fail(HDG_EINVAL, "hdg_refine: NULL pointer (batch, batch->ybits, probs, groups, ut, "
                             "rq or workspace)");
-  if ((uintptr_t)workspace & 7u)
-    return fail(HDG_EINVAL, "hdg_refine: workspace must be 8-byte aligned");
+  if (const int rc = ut_check_workspace(workspace, "hdg_refine")) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nc = s->nc;
-  hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)rf_tiles(nc), (unsigned)s->batch),
+  hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
                      dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule, tp);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return fail((int)e, "hdg_refine: launch (weights): %s", hipGetErrorString(e));
+  if (const int rc = ut_launched("hdg_refine", "weights")) return rc;
   hipLaunchKernelGGL(k_rf_sweep, dim3((unsigned)s->batch), dim3(RF_NT), 0, st,
                      (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
                      (long long*)rq, nc, (int)max_sweeps);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail((int)e, "hdg_refine: launch (sweep): %s", hipGetErrorString(e));
-  return 0;
+  return ut_launched("hdg_refine", "sweep");
 }

@@ -24,6 +24,7 @@ static_assert(UT_PER == 2, "the scan of the curve takes two rows per thread");
 // Whole block of UT_CLOSE_NT threads, uniform control flow, block synchronised on entry.
 //   par, comp   UT_MAXN words each, free on entry (the walk's forest; ranks, then boundaries)
 //   nxt         2 * UT_MAXN words, free on entry (the lists' links | their tails)
+//   yb          the commit's label rows (ut_label_rows)
 //   pq(k, x, y) the ends of merge k < M, read by thread 0 only
 //   nans        the commit's not-an-edge pairs (thread 0's value is used)
 // The function's own arrays (true groups, positions, the per-merge counts) are LDS of the
@@ -46,12 +47,7 @@ __device__ __forceinline__ void tc_close(uint32_t* par, uint32_t* comp, uint32_t
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n1 = nc - 1;
 
-  // ---- true groups: the set bits of the commit's label rows -------------------------------
-  for (int i = tid; i < nc; i += UT_CLOSE_NT) par[i] = (uint32_t)i;
-  __syncthreads();
-  ut_unite_labels(par, yb, nc);
-  __syncthreads();
-  const uint32_t TG = ut_label(par, comp, t, wsum, nc);
+  const uint32_t TG = ut_true_groups(par, comp, t, wsum, yb, nc);
   if (tg)
     for (int i = tid; i < nc; i += UT_CLOSE_NT) tg[i] = (int32_t)t[i];
 
@@ -136,8 +132,7 @@ __device__ __forceinline__ void tc_close(uint32_t* par, uint32_t* comp, uint32_t
       if (same) atomicAdd(&dss[mx], same);
     }
   }
-  st = ut_wave_sum(st);
-  if (lane == 0) red[wave] = st;
+  ut_count_put(red, st);
   __syncthreads();
 
   // ---- curve: inclusive scan over k, rows 2 tid and 2 tid + 1 ------------------------------
@@ -176,8 +171,7 @@ __device__ __forceinline__ void tc_close(uint32_t* par, uint32_t* comp, uint32_t
     cv[2 * k0 + 3] = k0 + 1 < M ? cs0 + s1 : tots;
   }
   if (tid == 0) {
-    unsigned long long sts = 0;
-    for (int w = 0; w < UT_CLOSE_WAVES; ++w) sts += red[w];
+    const unsigned long long sts = ut_count_sum<unsigned long long, UT_CLOSE_WAVES>(red, 0);
     row[HDG_LK_MERGES] = (unsigned long long)M;
     row[HDG_LK_TGROUPS] = TG;
     row[HDG_LK_ST] = sts;

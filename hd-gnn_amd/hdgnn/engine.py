@@ -364,6 +364,47 @@ class Engine:
                                         self._stream()))
         return self.probs, self.logits, self.ce_sum
 
+    # ---- what the decoders of the pair scores share --------------------------------
+    def _decode_probs(self, probs):
+        """`probs`, default self.probs, checked: contiguous fp32 [B][2][nc(nc-1)] on this device."""
+        probs = self.probs if probs is None else probs
+        if (probs.device != self.device or probs.dtype != torch.float32
+                or not probs.is_contiguous()
+                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
+            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
+                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        return probs
+
+    @staticmethod
+    def _rule(rule):
+        """The library's number of the link rule `rule`."""
+        if rule not in _lib.UT_RULES:
+            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        return _lib.UT_RULES[rule]
+
+    def _workspace(self, attr, nbytes_fn, dtype):
+        """The workspace kept in self.<attr>: nbytes_fn() bytes of `dtype`, allocated on the
+        first call."""
+        ws = getattr(self, attr, None)
+        if ws is None:
+            nbytes = nbytes_fn()
+            if nbytes == 0:
+                raise RuntimeError(self.lib.hdg_last_error().decode())
+            ws = torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=self.device)
+            setattr(self, attr, ws)
+        return ws
+
+    def _tree_outputs(self):
+        """Fresh (merges, levels, curve, tgroups, lk) of a merge tree.  curve and lk hold u32 /
+        u64 counts, every value < 2^31 (at most nc (nc-1) / 2 pairs): int32 and int64 read
+        them as they are."""
+        n1 = self.nc - 1
+        return (torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device),
+                torch.empty(self.batch, n1, dtype=torch.float32, device=self.device),
+                torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device),
+                torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device),
+                torch.empty(self.batch, _lib.LK_SLOTS, dtype=torch.int64, device=self.device))
+
     def evaluate(self, dbatch, probs=None):
         """hdg_eval: the per-commit evaluation table of `probs` ([B][2][nc(nc-1)] fp32 on
         this device; default self.probs as the last forward / fwd_bwd / train step left it)
@@ -371,12 +412,7 @@ class Engine:
         FN, TN, U2, NAN; hdgnn.metrics.scores_from_counts turns it into scores).  Enqueued on
         the current stream; nothing is copied to the host."""
         self._check(dbatch)
-        probs = self.probs if probs is None else probs
-        if (probs.device != self.device or probs.dtype != torch.float32
-                or not probs.is_contiguous()
-                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
-            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
-                             % (self.batch, self.nc * (self.nc - 1), self.device))
+        probs = self._decode_probs(probs)
         # the library writes u64 counts; every value is < 2^63, so int64 reads them as they are
         ev = torch.empty(self.batch, _lib.EV_SLOTS, dtype=torch.int64, device=self.device)
         b = dbatch.struct()
@@ -394,29 +430,20 @@ class Engine:
         ut into scores).  Enqueued on the current stream; nothing is copied to the host.  The
         workspace is allocated on the first call and kept."""
         self._check(dbatch)
-        probs = self.probs if probs is None else probs
-        if (probs.device != self.device or probs.dtype != torch.float32
-                or not probs.is_contiguous()
-                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
-            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
-                             % (self.batch, self.nc * (self.nc - 1), self.device))
-        if rule not in _lib.UT_RULES:
-            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
-        if getattr(self, "_ut_workspace", None) is None:
-            nbytes = self.lib.hdg_untangle_workspace_bytes(ctypes.byref(self.shape))
-            if nbytes == 0:
-                raise RuntimeError(self.lib.hdg_last_error().decode())
-            self._ut_workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=self.device)
+        probs = self._decode_probs(probs)
+        rule = self._rule(rule)
+        ws = self._workspace("_ut_workspace", lambda: self.lib.hdg_untangle_workspace_bytes(
+            ctypes.byref(self.shape)), torch.int32)
         groups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
         # u64 counts, every value < 2^63: int64 reads them as they are
         ut = torch.empty(self.batch, _lib.UT_SLOTS, dtype=torch.int64, device=self.device)
         b = dbatch.struct()
         _lib.check(self.lib.hdg_untangle(ctypes.byref(self.shape), ctypes.byref(b),
                                          ctypes.c_void_p(probs.data_ptr()),
-                                         ctypes.c_float(threshold), _lib.UT_RULES[rule],
+                                         ctypes.c_float(threshold), rule,
                                          ctypes.c_void_p(groups.data_ptr()), None,
                                          ctypes.c_void_p(ut.data_ptr()),
-                                         ctypes.c_void_p(self._ut_workspace.data_ptr()),
+                                         ctypes.c_void_p(ws.data_ptr()),
                                          self._stream()))
         return groups, ut
 
@@ -430,36 +457,20 @@ class Engine:
         curve and lk into the best threshold).  Enqueued on the current stream; nothing is
         copied to the host.  The workspace is allocated on the first call and kept."""
         self._check(dbatch)
-        probs = self.probs if probs is None else probs
-        if (probs.device != self.device or probs.dtype != torch.float32
-                or not probs.is_contiguous()
-                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
-            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
-                             % (self.batch, self.nc * (self.nc - 1), self.device))
-        if rule not in _lib.UT_RULES:
-            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
-        if getattr(self, "_lk_workspace", None) is None:
-            nbytes = self.lib.hdg_linkage_workspace_bytes(ctypes.byref(self.shape))
-            if nbytes == 0:
-                raise RuntimeError(self.lib.hdg_last_error().decode())
-            self._lk_workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
-        n1 = self.nc - 1
-        merges = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
-        levels = torch.empty(self.batch, n1, dtype=torch.float32, device=self.device)
-        # u32 / u64 counts, every value < 2^31 (at most nc (nc-1) / 2 pairs): int32 and int64
-        # read them as they are
-        curve = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
-        tgroups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
-        lk = torch.empty(self.batch, _lib.LK_SLOTS, dtype=torch.int64, device=self.device)
+        probs = self._decode_probs(probs)
+        rule = self._rule(rule)
+        ws = self._workspace("_lk_workspace", lambda: self.lib.hdg_linkage_workspace_bytes(
+            ctypes.byref(self.shape)), torch.int64)
+        merges, levels, curve, tgroups, lk = self._tree_outputs()
         b = dbatch.struct()
         _lib.check(self.lib.hdg_linkage(ctypes.byref(self.shape), ctypes.byref(b),
-                                        ctypes.c_void_p(probs.data_ptr()), _lib.UT_RULES[rule],
+                                        ctypes.c_void_p(probs.data_ptr()), rule,
                                         ctypes.c_void_p(merges.data_ptr()),
                                         ctypes.c_void_p(levels.data_ptr()),
                                         ctypes.c_void_p(curve.data_ptr()),
                                         ctypes.c_void_p(tgroups.data_ptr()),
                                         ctypes.c_void_p(lk.data_ptr()),
-                                        ctypes.c_void_p(self._lk_workspace.data_ptr()),
+                                        ctypes.c_void_p(ws.data_ptr()),
                                         self._stream()))
         return merges, levels, curve, tgroups, lk
 
@@ -471,38 +482,24 @@ class Engine:
         untangle()'s.  Enqueued on the current stream; nothing is copied to the host.  The
         workspace is allocated on the first call and kept."""
         self._check(dbatch)
-        probs = self.probs if probs is None else probs
-        if (probs.device != self.device or probs.dtype != torch.float32
-                or not probs.is_contiguous()
-                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
-            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
-                             % (self.batch, self.nc * (self.nc - 1), self.device))
-        if rule not in _lib.UT_RULES:
-            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        probs = self._decode_probs(probs)
+        rule = self._rule(rule)
         if method not in _lib.AG_METHODS:
             raise ValueError("method must be one of %s (got %r)"
                              % (", ".join(_lib.AG_METHODS), method))
-        if getattr(self, "_ag_workspace", None) is None:
-            nbytes = self.lib.hdg_agglomerate_workspace_bytes(ctypes.byref(self.shape), 0)
-            if nbytes == 0:
-                raise RuntimeError(self.lib.hdg_last_error().decode())
-            self._ag_workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-        n1 = self.nc - 1
-        merges = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
-        levels = torch.empty(self.batch, n1, dtype=torch.float32, device=self.device)
-        curve = torch.empty(self.batch, n1, 2, dtype=torch.int32, device=self.device)
-        tgroups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
-        lk = torch.empty(self.batch, _lib.LK_SLOTS, dtype=torch.int64, device=self.device)
+        ws = self._workspace("_ag_workspace", lambda: self.lib.hdg_agglomerate_workspace_bytes(
+            ctypes.byref(self.shape), 0), torch.float32)
+        merges, levels, curve, tgroups, lk = self._tree_outputs()
         b = dbatch.struct()
         _lib.check(self.lib.hdg_agglomerate(ctypes.byref(self.shape), ctypes.byref(b),
                                             ctypes.c_void_p(probs.data_ptr()),
-                                            _lib.UT_RULES[rule], _lib.AG_METHODS[method], 0,
+                                            rule, _lib.AG_METHODS[method], 0,
                                             ctypes.c_void_p(merges.data_ptr()),
                                             ctypes.c_void_p(levels.data_ptr()),
                                             ctypes.c_void_p(curve.data_ptr()),
                                             ctypes.c_void_p(tgroups.data_ptr()),
                                             ctypes.c_void_p(lk.data_ptr()),
-                                            ctypes.c_void_p(self._ag_workspace.data_ptr()),
+                                            ctypes.c_void_p(ws.data_ptr()),
                                             self._stream()))
         return merges, levels, curve, tgroups, lk
 
@@ -521,15 +518,14 @@ class Engine:
                     or tuple(x.shape) != shp):
                 raise ValueError("merges, levels, curve and lk must be the contiguous tensors "
                                  "linkage() / agglomerate() return for this engine")
-        if rule not in _lib.UT_RULES:
-            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        rule = self._rule(rule)
         groups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
         ut = torch.empty(self.batch, _lib.CUT_SLOTS, dtype=torch.int64, device=self.device)
         _lib.check(self.lib.hdg_cut(ctypes.byref(self.shape), ctypes.c_void_p(merges.data_ptr()),
                                     ctypes.c_void_p(levels.data_ptr()),
                                     ctypes.c_void_p(curve.data_ptr()),
                                     ctypes.c_void_p(lk.data_ptr()), ctypes.c_float(threshold),
-                                    _lib.UT_RULES[rule], ctypes.c_void_p(groups.data_ptr()),
+                                    rule, ctypes.c_void_p(groups.data_ptr()),
                                     ctypes.c_void_p(ut.data_ptr()), self._stream()))
         return groups, ut
 
@@ -545,14 +541,8 @@ class Engine:
         untangle()'s.  Enqueued on the current stream; nothing is copied to the host.  The
         workspace is allocated on the first call and kept."""
         self._check(dbatch)
-        probs = self.probs if probs is None else probs
-        if (probs.device != self.device or probs.dtype != torch.float32
-                or not probs.is_contiguous()
-                or tuple(probs.shape) != (self.batch, 2, self.nc * (self.nc - 1))):
-            raise ValueError("probs must be a contiguous float32 [%d][2][%d] tensor on %s"
-                             % (self.batch, self.nc * (self.nc - 1), self.device))
-        if rule not in _lib.UT_RULES:
-            raise ValueError("rule must be one of %s (got %r)" % (", ".join(_lib.UT_RULES), rule))
+        probs = self._decode_probs(probs)
+        rule = self._rule(rule)
         if not (isinstance(max_sweeps, int) and 1 <= max_sweeps <= _lib.RF_MAX_SWEEPS):
             raise ValueError("max_sweeps must be an int in [1, %d] (got %r)"
                              % (_lib.RF_MAX_SWEEPS, max_sweeps))
@@ -561,11 +551,8 @@ class Engine:
                                    or tuple(groups.shape) != (self.batch, self.nc)):
             raise ValueError("groups must be a contiguous int32 [%d][%d] tensor on %s"
                              % (self.batch, self.nc, self.device))
-        if getattr(self, "_rf_workspace", None) is None:
-            nbytes = self.lib.hdg_refine_workspace_bytes(ctypes.byref(self.shape), 0)
-            if nbytes == 0:
-                raise RuntimeError(self.lib.hdg_last_error().decode())
-            self._rf_workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        ws = self._workspace("_rf_workspace", lambda: self.lib.hdg_refine_workspace_bytes(
+            ctypes.byref(self.shape), 0), torch.int64)
         out = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
         # u64 counts, every value < 2^63: int64 reads them as they are
         ut = torch.empty(self.batch, _lib.RF_SLOTS, dtype=torch.int64, device=self.device)
@@ -573,13 +560,12 @@ class Engine:
         b = dbatch.struct()
         _lib.check(self.lib.hdg_refine(ctypes.byref(self.shape), ctypes.byref(b),
                                        ctypes.c_void_p(probs.data_ptr()),
-                                       ctypes.c_float(threshold), _lib.UT_RULES[rule],
-                                       max_sweeps, 0,
+                                       ctypes.c_float(threshold), rule, max_sweeps, 0,
                                        None if groups is None
                                        else ctypes.c_void_p(groups.data_ptr()),
                                        ctypes.c_void_p(out.data_ptr()),
                                        ctypes.c_void_p(ut.data_ptr()),
                                        ctypes.c_void_p(rq.data_ptr()),
-                                       ctypes.c_void_p(self._rf_workspace.data_ptr()),
+                                       ctypes.c_void_p(ws.data_ptr()),
                                        self._stream()))
         return out, ut, rq

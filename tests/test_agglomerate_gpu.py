@@ -10,19 +10,18 @@ Shapes: nc 2 and 3 (one and two merges), 33, the tile edges 64 / 65, 74 (the gli
 the workspace; B = 3, but B = 1 and rule "mean" only at the two largest.
 """
 import ctypes
-import math
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from _decode import (B, T, _cut, _linkage_run, _onehot, _pairs, _planted, _planted_labels, _probs,
+                     _same, _uniform, _untangle_run, _with_infs, _with_nans)
+from _decode import _AgglomerateBufs as _Bufs
+from _decode import _agglomerate_run as _run
 from hdgnn import _lib, data, layout, metrics
 from hdgnn.synth import synth_commits
-from test_untangle_gpu import B, T, _onehot, _pairs, _planted, _planted_labels, _probs, _sym, _uniform
-from test_untangle_gpu import _run as _untangle_run
-from test_linkage_gpu import _run as _linkage_run
-from test_linkage_gpu import _same
 
 pytestmark = pytest.mark.gpu
 
@@ -52,78 +51,6 @@ def _rules(nc):
 # ---------------------------------------------------------------------------------------
 # running the library and the host
 # ---------------------------------------------------------------------------------------
-class _Bufs:
-    """Poisoned outputs and workspace: the call writes every slot itself."""
-
-    def __init__(self, nb, nc, dev, flags=0):
-        shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-        nbytes = _lib.load().hdg_agglomerate_workspace_bytes(ctypes.byref(shape), flags)
-        assert nbytes == nb * nc * nc * 4
-        self.merges = torch.full((nb, nc - 1, 2), -7, dtype=torch.int32, device=dev)
-        self.levels = torch.full((nb, nc - 1), 12345.0, dtype=torch.float32, device=dev)
-        self.curve = torch.full((nb, nc - 1, 2), -7, dtype=torch.int32, device=dev)
-        self.tgroups = torch.full((nb, nc), -7, dtype=torch.int32, device=dev)
-        self.lk = torch.full((nb, _lib.LK_SLOTS), -1, dtype=torch.int64, device=dev)
-        self.ws = torch.full((nbytes // 4,), 0x7F7F7F7F, dtype=torch.int32, device=dev)
-
-    def outputs(self):
-        return (self.merges, self.levels, self.curve, self.tgroups, self.lk)
-
-    def poisoned(self):
-        return bool((self.merges == -7).all() and (self.levels == 12345.0).all()
-                    and (self.curve == -7).all() and (self.tgroups == -7).all()
-                    and (self.lk == -1).all() and (self.ws == 0x7F7F7F7F).all())
-
-    def read(self):
-        return tuple(x.cpu().numpy() for x in self.outputs())
-
-
-def _run(y, p1, rule="mean", method="average", flags=0, bufs=None, tgroups=True):
-    """hdg_agglomerate on relation labels y (b, R) and scores p1 (b, R) -> (bufs, the five
-    outputs as numpy arrays read back from the device)."""
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    nb, R = p1.shape
-    nc = int(round((1 + math.sqrt(1 + 4 * R)) / 2))
-    ybits = torch.from_numpy(data.pack_bits(data._grid(y, nc)).view(np.int32)).to(dev)
-    pt = torch.from_numpy(_probs(p1)).to(dev).contiguous()
-    bufs = bufs or _Bufs(nb, nc, dev, flags)
-    shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-    bt = _lib.Batch(None, None, ybits.data_ptr(), None, None, None)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    vp = ctypes.c_void_p
-    _lib.check(lib.hdg_agglomerate(ctypes.byref(shape), ctypes.byref(bt), vp(pt.data_ptr()),
-                                   _lib.UT_RULES[rule], _lib.AG_METHODS[method], flags,
-                                   vp(bufs.merges.data_ptr()), vp(bufs.levels.data_ptr()),
-                                   vp(bufs.curve.data_ptr()),
-                                   vp(bufs.tgroups.data_ptr()) if tgroups else None,
-                                   vp(bufs.lk.data_ptr()), vp(bufs.ws.data_ptr()), stream))
-    torch.cuda.synchronize(dev)
-    return bufs, bufs.read()
-
-
-def _cut(nc, merges, levels, curve, lk, thr, rule, ut=True):
-    """hdg_cut on numpy trees -> (groups, ut) read back; buffers poisoned before the call."""
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    nb = len(levels)
-    vp = ctypes.c_void_p
-    tm = torch.from_numpy(np.ascontiguousarray(merges, np.int32)).to(dev)
-    tl = torch.from_numpy(np.ascontiguousarray(levels, np.float32)).to(dev)
-    tc = torch.from_numpy(np.ascontiguousarray(curve).astype(np.int32)).to(dev)
-    tk = torch.from_numpy(np.ascontiguousarray(lk, np.int64)).to(dev)
-    groups = torch.full((nb, nc), -7, dtype=torch.int32, device=dev)
-    row = torch.full((nb, _lib.CUT_SLOTS), -1, dtype=torch.int64, device=dev)
-    shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.hdg_cut(ctypes.byref(shape), vp(tm.data_ptr()), vp(tl.data_ptr()),
-                           vp(tc.data_ptr()) if ut else None, vp(tk.data_ptr()) if ut else None,
-                           ctypes.c_float(thr), _lib.UT_RULES[rule], vp(groups.data_ptr()),
-                           vp(row.data_ptr()) if ut else None, stream))
-    torch.cuda.synchronize(dev)
-    return groups.cpu().numpy(), row.cpu().numpy()
-
-
 _HOST = {}
 
 
@@ -151,22 +78,6 @@ def _check(key, y, p1, rules=RULES, methods=METHODS, flags=0):
 # ---------------------------------------------------------------------------------------
 # inputs
 # ---------------------------------------------------------------------------------------
-def _with_nans(nc, nb):
-    """NaN in one direction of about 5% of the pairs, and in commit 1 a hunk no edge reaches."""
-    y, p1 = _planted(nc, seed=300 + nc, nb=nb)
-    rng = np.random.default_rng(300 + nc)
-    I, J = _pairs(nc)
-    hit = _sym(nc, rng, nb, 0.05)
-    hit[:, (I == 0) & (J == 1)] = hit[:, (I == 1) & (J == 0)] = True
-    first = _sym(nc, rng, nb, 0.5) ^ (I < J)
-    p1 = p1.copy()
-    p1[hit & first] = np.nan
-    if nc >= 33 and nb > 1:
-        p1[1, I == 7] = np.nan
-        hit[1, (I == 7) | (J == 7)] = True
-    return y, p1, hit.sum(1) // 2
-
-
 def _encoded(nc, nb):
     """test_scores_that_encode_their_relation's scores: neither symmetric nor smooth in (p, q)."""
     I, J = _pairs(nc)
@@ -211,6 +122,24 @@ def test_nan_in_one_direction_and_an_isolated_hunk(nc):
         np.testing.assert_array_equal(lk[:, _lib.LK_NAN], nans)
         if nc >= 33:
             assert lk[1, _lib.LK_MERGES] <= nc - 2
+
+
+@pytest.mark.parametrize("nc", [3, T + 1])
+def test_infinite_scores(nc):
+    """Under mean a pair of +inf and -inf is no edge and counts in LK_NAN; hdg_untangle's
+    UT_NAN, which counts NaN scores, stays 0 on the same input."""
+    y, p1 = _with_infs(*_planted(nc, seed=50 + nc), seed=50 + nc)
+    key, methods = "inf %d" % nc, METHODS if nc == 3 else ("average",)
+    with np.errstate(invalid="ignore"):             # _check's np.diff of two infinite levels
+        _check(key, y, p1, methods=methods)
+        if nc == 3:
+            _check(key, y, p1, flags=_lib.AG_FLAG_GLOBAL)
+    for method in methods:
+        mean = _host(key, y, p1, "mean", method)[4][:, _lib.LK_NAN]
+        both = _host(key, y, p1, "both", method)[4][:, _lib.LK_NAN]
+        assert (mean >= 1).all() and (both == 0).all()
+    ut = metrics.untangle_counts(_onehot(y), _probs(p1), 0.5, "mean")[0]
+    assert (ut[:, _lib.UT_NAN] == 0).all()
 
 
 @pytest.mark.parametrize("nc", [33, T + 1, 2 * T + 1])

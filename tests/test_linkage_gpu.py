@@ -7,19 +7,19 @@ edges test_untangle_gpu derives from the header constants: nc 2, 33, 64, 65, 74,
 193 at B = 3, and nc 705 at B = 1 for the 16-block cap.
 """
 import ctypes
-import math
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from _decode import (B, BIG, NC_CAPPED, NC_THREE, NC_TWO, SHAPES, T, _bridged_groups, _onehot,
+                     _owner, _pairs, _planted, _planted_labels, _probs, _same, _scores_of, _sym,
+                     _uniform, _untangle_run, _with_infs)
+from _decode import _LinkageBufs as _Bufs
+from _decode import _linkage_run as _run
 from hdgnn import _lib, data, layout, metrics
 from hdgnn.synth import synth_commits
-from test_untangle_gpu import (B, BIG, NC_CAPPED, NC_THREE, NC_TWO, SHAPES, T, _bridged_groups,
-                               _onehot, _owner, _pairs, _planted, _planted_labels, _probs,
-                               _scores_of, _sym, _uniform)
-from test_untangle_gpu import _run as _untangle_run
 
 pytestmark = pytest.mark.gpu
 
@@ -38,65 +38,6 @@ def test_shapes_are_the_block_edges():
 # ---------------------------------------------------------------------------------------
 # running the library and the host
 # ---------------------------------------------------------------------------------------
-class _Bufs:
-    """Poisoned outputs and workspace: the call writes every slot itself."""
-
-    def __init__(self, nb, nc, dev):
-        shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-        nbytes = _lib.load().hdg_linkage_workspace_bytes(ctypes.byref(shape))
-        assert nbytes == nb * _lib.untangle_blocks(nc) * nc * 8
-        self.merges = torch.full((nb, nc - 1, 2), -7, dtype=torch.int32, device=dev)
-        self.levels = torch.full((nb, nc - 1), 12345.0, dtype=torch.float32, device=dev)
-        self.curve = torch.full((nb, nc - 1, 2), -7, dtype=torch.int32, device=dev)
-        self.tgroups = torch.full((nb, nc), -7, dtype=torch.int32, device=dev)
-        self.lk = torch.full((nb, _lib.LK_SLOTS), -1, dtype=torch.int64, device=dev)
-        self.ws = torch.full((nbytes // 8,), 0x7F7F7F7F7F7F7F7F, dtype=torch.int64, device=dev)
-
-    def poisoned(self):
-        return bool((self.merges == -7).all() and (self.levels == 12345.0).all()
-                    and (self.curve == -7).all() and (self.tgroups == -7).all()
-                    and (self.lk == -1).all() and (self.ws == 0x7F7F7F7F7F7F7F7F).all())
-
-    def read(self):
-        return tuple(x.cpu().numpy() for x in (self.merges, self.levels, self.curve, self.tgroups,
-                                               self.lk))
-
-
-def _run(y, p1, rule="mean", bufs=None, tgroups=True):
-    """hdg_linkage on relation labels y (b, R) and scores p1 (b, R) -> (bufs, the five outputs
-    as numpy arrays read back from the device)."""
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    nb, R = p1.shape
-    nc = int(round((1 + math.sqrt(1 + 4 * R)) / 2))
-    ybits = torch.from_numpy(data.pack_bits(data._grid(y, nc)).view(np.int32)).to(dev)
-    pt = torch.from_numpy(_probs(p1)).to(dev).contiguous()
-    bufs = bufs or _Bufs(nb, nc, dev)
-    shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-    bt = _lib.Batch(None, None, ybits.data_ptr(), None, None, None)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    vp = ctypes.c_void_p
-    _lib.check(lib.hdg_linkage(ctypes.byref(shape), ctypes.byref(bt), vp(pt.data_ptr()),
-                               _lib.UT_RULES[rule], vp(bufs.merges.data_ptr()),
-                               vp(bufs.levels.data_ptr()), vp(bufs.curve.data_ptr()),
-                               vp(bufs.tgroups.data_ptr()) if tgroups else None,
-                               vp(bufs.lk.data_ptr()), vp(bufs.ws.data_ptr()), stream))
-    torch.cuda.synchronize(dev)
-    return bufs, bufs.read()
-
-
-def _same(dev, host, what=""):
-    """The five device outputs == the host's."""
-    (m, lv, cv, t, lk), (hm, hlv, hcv, ht, hlk) = dev, host
-    np.testing.assert_array_equal(lk, hlk, what)
-    np.testing.assert_array_equal(m, hm, what)
-    pad = np.isnan(hlv)
-    np.testing.assert_array_equal(np.isnan(lv), pad, what)
-    np.testing.assert_array_equal(lv.view(np.uint32)[~pad], hlv.view(np.uint32)[~pad], what)
-    np.testing.assert_array_equal(cv, hcv, what)
-    np.testing.assert_array_equal(t, ht, what)
-
-
 def _check(y, p1, rule="mean", what=""):
     """Device == host, all five outputs; -> the host's."""
     _, dev = _run(y, p1, rule)
@@ -144,6 +85,17 @@ def test_nan_in_one_direction(nc):
         np.testing.assert_array_equal(lk[:, _lib.LK_NAN], hit.sum(1) // 2)
         if nc >= 33:
             assert lk[1, _lib.LK_MERGES] == nc - 2
+
+
+@pytest.mark.parametrize("nc", [3, T + 1])
+def test_infinite_scores(nc):
+    """Under mean a pair of +inf and -inf is no edge and counts in LK_NAN; hdg_untangle's
+    UT_NAN, which counts NaN scores, stays 0 on the same input."""
+    y, p1 = _with_infs(*_planted(nc, seed=50 + nc), seed=50 + nc)
+    nan = {rule: _check(y, p1, rule, "inf nc %d" % nc)[4][:, _lib.LK_NAN] for rule in RULES}
+    assert (nan["mean"] >= 1).all() and (nan["both"] == 0).all()
+    ut = metrics.untangle_counts(_onehot(y), _probs(p1), 0.5, "mean")[0]
+    assert (ut[:, _lib.UT_NAN] == 0).all()
 
 
 @pytest.mark.parametrize("nc", [33, T + 1, NC_TWO, NC_THREE])

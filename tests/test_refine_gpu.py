@@ -17,13 +17,13 @@ import numpy as np
 import pytest
 import torch
 
+from _decode import (B, T, _agglomerate_run, _cut, _onehot, _pairs, _planted, _probs, _uniform,
+                     _with_nans)
+from _decode import _RefineBufs as _Bufs
+from _decode import _refine_run as _run
 from conftest import ROOT
 from hdgnn import _lib, data, layout, metrics
 from hdgnn.synth import synth_commits
-from test_untangle_gpu import B, T, _onehot, _pairs, _planted, _probs, _uniform
-from test_untangle_gpu import _run as _untangle_run
-from test_agglomerate_gpu import _run as _agglomerate_run
-from test_agglomerate_gpu import _cut, _with_nans
 from test_refine import noisy_planted, wrong_first_merge
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,6 @@ RULES = ("mean", "any", "both")
 SHAPES = [2, 3, 33, T, T + 1, 74, 2 * T + 1]
 TWO_PER_THREAD = 1025
 SWEEPS = (1, 2, 8, 64)
-POISON_WS = 0x7F7F7F7F7F7F7F7F
 
 
 def test_shapes_follow_from_the_header_constants():
@@ -44,53 +43,6 @@ def test_shapes_follow_from_the_header_constants():
 # ---------------------------------------------------------------------------------------
 # running the library and the host
 # ---------------------------------------------------------------------------------------
-class _Bufs:
-    """Poisoned outputs and workspace: the call writes every slot itself."""
-
-    def __init__(self, nb, nc, dev):
-        shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-        nbytes = _lib.load().hdg_refine_workspace_bytes(ctypes.byref(shape), 0)
-        t = -(-nc // T)
-        assert nbytes % 8 == 0 and nbytes >= nb * (nc * nc + t * (t + 1) // 2) * 4
-        self.groups = torch.full((nb, nc), -7, dtype=torch.int32, device=dev)
-        self.ut = torch.full((nb, _lib.RF_SLOTS), -1, dtype=torch.int64, device=dev)
-        self.rq = torch.full((nb, _lib.RF_Q_SLOTS), -99, dtype=torch.int64, device=dev)
-        self.ws = torch.full((nbytes // 8,), POISON_WS, dtype=torch.int64, device=dev)
-
-    def poisoned(self):
-        return bool((self.groups == -7).all() and (self.ut == -1).all() and (self.rq == -99).all()
-                    and (self.ws == POISON_WS).all())
-
-
-def _run(y, p1, start=None, thr=0.5, rule="mean", max_sweeps=8, bufs=None, alias=False):
-    """hdg_refine on relation labels y (b, R), scores p1 (b, R) and starting ids (b, nc) or
-    None -> (bufs, groups, ut, rq) read back.  alias: groups_in is the output array itself."""
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    nb, R = p1.shape
-    nc = int(round((1 + math.sqrt(1 + 4 * R)) / 2))
-    ybits = torch.from_numpy(data.pack_bits(data._grid(y, nc)).view(np.int32)).to(dev)
-    pt = torch.from_numpy(_probs(p1)).to(dev).contiguous()
-    bufs = bufs or _Bufs(nb, nc, dev)
-    gin = None
-    if start is not None:
-        gin = torch.from_numpy(np.ascontiguousarray(start, np.int32)).to(dev)
-        if alias:
-            bufs.groups.copy_(gin)
-            gin = bufs.groups
-    shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-    bt = _lib.Batch(None, None, ybits.data_ptr(), None, None, None)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    vp = ctypes.c_void_p
-    _lib.check(lib.hdg_refine(ctypes.byref(shape), ctypes.byref(bt), vp(pt.data_ptr()),
-                              ctypes.c_float(thr), _lib.UT_RULES[rule], max_sweeps, 0,
-                              None if gin is None else vp(gin.data_ptr()),
-                              vp(bufs.groups.data_ptr()), vp(bufs.ut.data_ptr()),
-                              vp(bufs.rq.data_ptr()), vp(bufs.ws.data_ptr()), stream))
-    torch.cuda.synchronize(dev)
-    return bufs, bufs.groups.cpu().numpy(), bufs.ut.cpu().numpy(), bufs.rq.cpu().numpy()
-
-
 def _same(dev, host, what=""):
     """(groups, ut, rq) of the device against (ut, groups, rq) of the host."""
     g, ut, rq = dev

@@ -21,31 +21,15 @@ import numpy as np
 import pytest
 import torch
 
+from _decode import (B, BIG, MAXB, NC_CAPPED, NC_THREE, NC_TWO, SHAPES, T, TPB, _bridged_groups,
+                     _onehot, _owner, _pairs, _planted, _planted_labels, _probs, _scores_of,
+                     _sym, _tile_pairs, _uniform, _with_infs)
+from _decode import _UntangleBufs as _Bufs
+from _decode import _untangle_run as _run
 from hdgnn import _lib, data, layout, metrics
 from hdgnn.synth import synth_commits
 
 pytestmark = pytest.mark.gpu
-
-B = 3
-T, TPB, MAXB = _lib.UT_TILE, _lib.UT_TILES_PER_BLOCK, _lib.UT_MAX_BLOCKS
-
-
-def _tile_pairs(nc):
-    t = -(-nc // T)
-    return t * (t + 1) // 2
-
-
-def _nc_blocks(k):
-    """Smallest nc whose commit runs on k blocks."""
-    nc = 2
-    while _lib.untangle_blocks(nc) < k:
-        nc += 1
-    return nc
-
-
-NC_TWO, NC_THREE, NC_CAPPED = _nc_blocks(2), _nc_blocks(3), 705
-SHAPES = [2, 33, T, T + 1, 74, NC_TWO - 1, NC_TWO, NC_THREE]
-BIG = [NC_TWO, NC_THREE]
 
 
 def test_shapes_are_the_block_edges():
@@ -62,53 +46,8 @@ def test_shapes_are_the_block_edges():
 # ---------------------------------------------------------------------------------------
 # running the library and the host
 # ---------------------------------------------------------------------------------------
-def _probs(p1):
-    """(b, R) scores -> C-contiguous (b, 2, R) float32 (fancy-indexed inputs may be F-ordered)."""
-    return np.ascontiguousarray(np.stack([1.0 - p1, p1], 1), np.float32)
-
-
-def _onehot(y):
-    return np.stack([1 - y, y], 1).astype(np.float32)
-
-
 def _host(y, p1, thr=0.5, rule="mean"):
     return metrics.untangle_counts(_onehot(y), _probs(p1), thr, rule)
-
-
-class _Bufs:
-    """Poisoned outputs and workspace: the call writes every slot itself."""
-
-    def __init__(self, nb, nc, dev):
-        shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-        nbytes = _lib.load().hdg_untangle_workspace_bytes(ctypes.byref(shape))
-        assert nbytes == nb * _lib.untangle_blocks(nc) * (nc + 2) * 4
-        self.groups = torch.full((nb, nc), -7, dtype=torch.int32, device=dev)
-        self.tgroups = torch.full((nb, nc), -7, dtype=torch.int32, device=dev)
-        self.ut = torch.full((nb, _lib.UT_SLOTS), -1, dtype=torch.int64, device=dev)
-        self.ws = torch.full((nbytes // 4,), 0x7F7F7F7F, dtype=torch.int32, device=dev)
-
-
-def _run(y, p1, thr=0.5, rule="mean", bufs=None, tgroups=True):
-    """hdg_untangle on relation labels y (b, R) and scores p1 (b, R) -> (bufs, groups,
-    tgroups, ut) as numpy arrays read back from the device."""
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    nb, R = p1.shape
-    nc = int(round((1 + math.sqrt(1 + 4 * R)) / 2))
-    ybits = torch.from_numpy(data.pack_bits(data._grid(y, nc)).view(np.int32)).to(dev)
-    pt = torch.from_numpy(_probs(p1)).to(dev).contiguous()
-    bufs = bufs or _Bufs(nb, nc, dev)
-    shape = _lib.Shape(nb, 20, nc, 2, nb, 0)
-    bt = _lib.Batch(None, None, ybits.data_ptr(), None, None, None)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.hdg_untangle(ctypes.byref(shape), ctypes.byref(bt),
-                                ctypes.c_void_p(pt.data_ptr()), ctypes.c_float(thr),
-                                _lib.UT_RULES[rule], ctypes.c_void_p(bufs.groups.data_ptr()),
-                                ctypes.c_void_p(bufs.tgroups.data_ptr()) if tgroups else None,
-                                ctypes.c_void_p(bufs.ut.data_ptr()),
-                                ctypes.c_void_p(bufs.ws.data_ptr()), stream))
-    torch.cuda.synchronize(dev)
-    return bufs, bufs.groups.cpu().numpy(), bufs.tgroups.cpu().numpy(), bufs.ut.cpu().numpy()
 
 
 def _check(y, p1, thr=0.5, rule="mean", what=""):
@@ -123,59 +62,6 @@ def _check(y, p1, thr=0.5, rule="mean", what=""):
     four = [_lib.UT_SS, _lib.UT_SD, _lib.UT_DS, _lib.UT_DD]
     assert (ut[:, four].sum(1) == nc * (nc - 1) // 2).all()
     return hut, hg, ht
-
-
-# ---------------------------------------------------------------------------------------
-# inputs
-# ---------------------------------------------------------------------------------------
-def _pairs(nc):
-    return data.pair_index(nc)
-
-
-def _sym(nc, rng, nb, prob):
-    """(nb, R) bool: a random symmetric choice of unordered pairs, each with probability prob."""
-    I, J = _pairs(nc)
-    m = rng.random((nb, nc, nc)) < prob
-    m = np.triu(m, 1)
-    m = m | m.transpose(0, 2, 1)
-    return m[:, I, J]
-
-
-def _planted_labels(nc, rng, nb, k=3, pad=2):
-    """Labels from k planted groups, each direction of a within-group pair set with
-    probability 0.5 on its own (not symmetric); the last `pad` hunks are padding: no labels."""
-    I, J = _pairs(nc)
-    gt = rng.integers(0, k, (nb, nc))
-    y = (gt[:, I] == gt[:, J]) & (rng.random((nb, len(I))) < 0.5)
-    y &= (I < nc - pad) & (J < nc - pad)
-    return y.astype(np.uint8)
-
-
-def _planted(nc, seed, nb=B):
-    """Planted predicted groups of about 12 hunks with sparse within-group links (a pair of
-    the same group is linked with probability 0.25: both directions high), a handful of
-    cross-group pairs high in ONE direction only, everything on a 1/256 grid; labels from
-    three other planted groups."""
-    rng = np.random.default_rng(seed)
-    I, J = _pairs(nc)
-    R = len(I)
-    kp = max(2, nc // 12)
-    gp = rng.integers(0, kp, (nb, nc))
-    same = gp[:, I] == gp[:, J]
-    on = same & _sym(nc, rng, nb, 0.25)
-    lo = rng.integers(0, 96, (nb, R))
-    hi = rng.integers(160, 257, (nb, R))
-    # about 1.5 per group; high + low = 160 .. 351 of 256, so about a quarter of them link
-    one_way = ~same & (rng.random((nb, R)) < 1.5 * kp / R)
-    p1 = (np.where(on | one_way, hi, lo) / 256.0).astype(np.float32)
-    pad = (I >= nc - 2) | (J >= nc - 2)
-    p1[:, pad] = 0.0
-    return _planted_labels(nc, rng, nb), p1
-
-
-def _uniform(nc, seed, nb=B):
-    rng = np.random.default_rng(100 + seed)
-    return _planted_labels(nc, rng, nb), rng.random((nb, nc * (nc - 1)), dtype=np.float32)
 
 
 # ---------------------------------------------------------------------------------------
@@ -251,6 +137,18 @@ def test_nan_in_one_direction(nc):
     assert not (nan & nan.transpose(0, 2, 1)).any() and nan.sum() == n_hit.sum()
 
 
+@pytest.mark.parametrize("nc", [3, T + 1])
+def test_infinite_scores(nc):
+    """Under mean a pair of +inf and -inf has a NaN weight: it does not link, and it is not in
+    UT_NAN, which counts NaN scores -- though hdg_linkage counts it as no edge."""
+    y, p1 = _with_infs(*_planted(nc, seed=50 + nc), seed=50 + nc)
+    for rule in ("mean", "any", "both"):
+        ut, _, _ = _check(y, p1, 0.5, rule, "inf nc %d" % nc)
+        assert (ut[:, _lib.UT_NAN] == 0).all()
+    lk = metrics.linkage(_onehot(y), _probs(p1), "mean")[4]
+    assert (lk[:, _lib.LK_NAN] >= 1).all()
+
+
 def test_capped_shape_sixteen_blocks():
     """nc 705, one commit: two interleaved paths (even hunks, odd hunks) whose links lie in
     every tile pair near the diagonal, a star across all tile rows on hunk 3, and a clique."""
@@ -273,53 +171,6 @@ def test_capped_shape_sixteen_blocks():
 # ---------------------------------------------------------------------------------------
 # structures that break a wrong union-find or a wrong merge of the blocks' forests
 # ---------------------------------------------------------------------------------------
-def _scores_of(nc, edges, directed=None):
-    """(R,) scores: 0.75 on the listed pairs (both directions; directed='down': only from
-    the higher hunk to the lower, 'up': only from the lower to the higher), 0.125 elsewhere."""
-    S = np.full((nc, nc), 0.125, np.float32)
-    e = np.asarray(edges, np.int64).reshape(-1, 2)
-    lo, hi = e.min(1), e.max(1)
-    if directed != "down":
-        S[lo, hi] = 0.75
-    if directed != "up":
-        S[hi, lo] = 0.75
-    I, J = _pairs(nc)
-    return S[I, J]
-
-
-def _owner(nc):
-    """(nc, nc) block that owns the tile pair of the unordered pair {p, q}."""
-    t = -(-nc // T)
-    k_of = np.zeros((t, t), np.int64)
-    k = 0
-    for i in range(t):
-        for j in range(i, t):
-            k_of[i, j] = k_of[j, i] = k
-            k += 1
-    tile = np.arange(nc) // T
-    return k_of[tile[:, None], tile[None, :]] % _lib.untangle_blocks(nc)
-
-
-def _bridged_groups(nc):
-    """Two groups whose links all lie in tile pairs of block 0 and whose only connecting link
-    lies in a tile pair of another block -> (edges, members of A, members of B, bridge)."""
-    own = _owner(nc)
-    A = list(range(10))                                        # a clique in tile pair (0, 0)
-    assert (own[:10, :10] == 0).all()
-    for q in range(10, nc):                                    # B's end of the bridge
-        if own[A[4], q] == 0:
-            continue
-        for h in range(nc - 1, 9, -1):                         # B is a star on h, q one of its rays
-            if h == q or own[q, h] != 0:
-                continue
-            rest = [r for r in range(10, nc) if r not in (q, h) and own[h, r] == 0]
-            if len(rest) >= 5:
-                Bm = [q, h] + rest[::max(1, len(rest) // 5)][:5]    # spread over the tiles
-                edges = [(a, b) for a in A for b in A if a < b] + [(h, r) for r in Bm if r != h]
-                return edges, A, Bm, (A[4], q)
-    raise AssertionError("no bridge at nc %d" % nc)
-
-
 @pytest.mark.parametrize("nc", BIG)
 def test_paths_stars_cliques(nc):
     rng = np.random.default_rng(400 + nc)
