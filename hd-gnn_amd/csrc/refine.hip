@@ -30,6 +30,16 @@
 //                 the final slots and the label graph are labelled (ut_label, ut_true_groups),
 //                 the pairs counted (ut_pair_counts, ut_pair_table), and groups, ut and rq
 //                 written.
+//
+// hdg_refine_ladder is the same two kernel bodies, each stated once (rf_weights, rf_sweep):
+//   k_rl_weights  rf_weights storing the fp32 weight of a pair instead of its gain at one
+//                 bound; one canonical NaN for a pair that is no edge and on the diagonal.
+//   k_rl_sweep    rf_sweep on a grid (rungs, B), the rung on blockIdx.x: a matrix word becomes
+//                 a gain by rf_gain on the stored w against the rung's bound (hdg_refine's
+//                 bits: the same function of the same w), the bounds a by-value argument.  The
+//                 start is the tree's cut at the rung: k_cut's unions (ut_union, levels > t'
+//                 strictly, rows of -1 / NaN skipped) and ut_label in the LDS arrays of the
+//                 sums, which are free before the sweeps; bounded by nc - 1.
 // Integer results only; the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -62,11 +72,33 @@ __device__ __forceinline__ int32_t rf_gain(const float w, const float tp) {
   return (int32_t)rintf(fminf(fmaxf(d, -2.f), 2.f) * RF_SCALE);
 }
 
-__global__ __launch_bounds__(UT_LINK_NT) void k_rf_weights(const float* __restrict__ probs,
-                                                           int32_t* __restrict__ ws, const int nc,
-                                                           const int rule, const float tp) {
+// The canonical word of a pair that is no edge in the matrix of weights (hdg_refine_ladder):
+// one quiet NaN.  ut_weight never returns a NaN weight for an edge.
+constexpr int32_t RL_NONE = 0x7FC00000;
+
+// what the matrix holds for a pair: hdg_refine's gain against the one bound of the call ...
+struct rf_as_gain {
+  float tp;
+  __device__ __forceinline__ int32_t operator()(const bool edge, const float w) const {
+    return edge ? rf_gain(w, tp) : 0;
+  }
+};
+// ... or the fp32 weight itself, for every rung of hdg_refine_ladder to form its gain from
+struct rl_as_weight {
+  __device__ __forceinline__ int32_t operator()(const bool edge, const float w) const {
+    return edge ? __float_as_int(w) : RL_NONE;
+  }
+};
+
+// The weights kernel of both entry points: staging, the pass by rows of the segment and the
+// pass by rows of the mirror, the no-edge count.  `word` says what is stored for a pair
+// (edge, w); the diagonal holds the word of a pair that is no edge.
+template <class Word>
+__device__ __forceinline__ void rf_weights(const float* __restrict__ probs,
+                                           int32_t* __restrict__ ws, const int nc, const int rule,
+                                           const Word word) {
   __shared__ float sa[UT_T * UT_LD];       // sa[a][c] = s(64 I + a, 64 J + c)
-  __shared__ float sb[UT_T * UT_LD];       // sb[c][a] = s(64 J + c, 64 I + a), then a's bits
+  __shared__ float sb[UT_T * UT_LD];       // sb[c][a] = s(64 J + c, 64 I + a), then the word's bits
   __shared__ uint32_t red[UT_LINK_WAVES];
 
   const int tid = threadIdx.x;
@@ -81,13 +113,14 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_rf_weights(const float* __restri
            [&](int, const int a, const int c, const int p, const int q, const float spq,
                const float sqp) {
              float w;
-             int32_t g = 0;
-             if (ut_weight(rule, spq, sqp, w)) g = rf_gain(w, tp);
-             else ++nans;
+             const bool edge = ut_weight(rule, spq, sqp, w);
+             if (!edge) ++nans;
+             const int32_t g = word(edge, w);
              wb[(size_t)p * nc + q] = g;
              sb[c * UT_LD + a] = __int_as_float(g);
            });
-  if (p0 == q0 && tid < UT_T && p0 + tid < nc) wb[(size_t)(p0 + tid) * (nc + 1)] = 0;     // (p, p)
+  if (p0 == q0 && tid < UT_T && p0 + tid < nc)
+    wb[(size_t)(p0 + tid) * (nc + 1)] = word(false, 0.f);                                 // (p, p)
   __syncthreads();
   ut_visit<true>(nc, p0, q0, sa, sb,       // by rows of the mirror: (q, p) for the p < q above
                  [&](int, int, int, const int p, const int q, float, const float gqp) {
@@ -98,6 +131,18 @@ __global__ __launch_bounds__(UT_LINK_NT) void k_rf_weights(const float* __restri
   if (tid == 0)
     reinterpret_cast<uint32_t*>(wb)[(size_t)nc * nc + blockIdx.x] =
         ut_count_sum<uint32_t, UT_LINK_WAVES>(red, 0);
+}
+
+__global__ __launch_bounds__(UT_LINK_NT) void k_rf_weights(const float* __restrict__ probs,
+                                                           int32_t* __restrict__ ws, const int nc,
+                                                           const int rule, const float tp) {
+  rf_weights(probs, ws, nc, rule, rf_as_gain{tp});
+}
+
+__global__ __launch_bounds__(UT_LINK_NT) void k_rl_weights(const float* __restrict__ probs,
+                                                           int32_t* __restrict__ ws, const int nc,
+                                                           const int rule) {
+  rf_weights(probs, ws, nc, rule, rl_as_weight{});
 }
 
 // a candidate of a step as one key: the larger key wins.  Value, then a non-empty slot
@@ -134,14 +179,33 @@ __device__ __forceinline__ long long rf_wave_sum64(long long v) {
   return v;
 }
 
-// groups_in and groups may be the same array: a commit's ids are all read before the first
-// barrier and written after the last
-__global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ ws,
-                                                    const uint32_t* __restrict__ ybits,
-                                                    const int32_t* gin, int32_t* groups,
-                                                    u64* __restrict__ ut,
-                                                    long long* __restrict__ rq, const int nc,
-                                                    const int max_sweeps) {
+// the bounds of a ladder's rungs, a by-value kernel argument
+struct rl_bounds {
+  float tp[HDG_RL_MAX_RUNGS];
+};
+
+// a word of the matrix as a gain: hdg_refine's matrix holds the gain; the ladder's holds the
+// weight, and rf_gain on the same w against the rung's bound is hdg_refine's gain bit for bit
+template <bool LADDER>
+__device__ __forceinline__ int32_t rf_word_gain(const int32_t word, const float tp) {
+  if constexpr (!LADDER) return word;
+  const float w = __int_as_float(word);
+  return w != w ? 0 : rf_gain(w, tp);
+}
+
+// The sweep block of both entry points, on one commit (and one rung): wb its matrix, yb its
+// label rows, and groups (or NULL), row and qrow where its outputs go.  The start is gin, the
+// commit's ids (or NULL) -- or with LADDER the cut of the commit's tree (merges, levels; or
+// NULL) at tp, k_cut's unions.  gin and groups may be the same array: a commit's ids are all
+// read before the first barrier and written after the last.
+template <bool LADDER>
+__device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
+                                         const uint32_t* __restrict__ yb, const int32_t* gin,
+                                         const int32_t* __restrict__ merges,
+                                         const float* __restrict__ levels, const float tp,
+                                         int32_t* groups, u64* __restrict__ row,
+                                         long long* __restrict__ qrow, const int nc,
+                                         const int max_sweeps) {
   __shared__ int32_t S[2][UT_MAXN];        // the per-slot sums of this step and the next
   __shared__ int32_t slot[UT_MAXN];
   __shared__ int32_t size[UT_MAXN];
@@ -154,8 +218,24 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
   __shared__ uint32_t red[UT_CLOSE_WAVES * 3];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x;
-  const int32_t* wb = ws + (size_t)b * rf_commit_words(nc);
+  bool started = gin != nullptr;           // uniform: a start other than every hunk alone
+
+  // ---- the tree's cut at tp, as k_cut unites it: ids in g; S is free before the sweeps ------
+  if constexpr (LADDER) {
+    if (merges) {                          // uniform
+      uint32_t* par = reinterpret_cast<uint32_t*>(S[0]);
+      for (int i = tid; i < nc; i += RF_NT) par[i] = (uint32_t)i;
+      __syncthreads();
+      for (int k = tid; k < nc - 1; k += RF_NT) {
+        const int32_t p = merges[2 * k], q = merges[2 * k + 1];
+        if (levels[k] > tp && p >= 0 && q >= 0 && p < nc && q < nc)      // NaN compares false
+          ut_union(par, (uint32_t)p, (uint32_t)q);
+      }
+      __syncthreads();
+      ut_label(par, reinterpret_cast<uint32_t*>(S[1]), g, wsum, nc);
+      started = true;
+    }
+  }
 
   // ---- start: a group sits in the slot of its smallest member -------------------------------
   int32_t id[UT_PER], my[UT_PER], nx[UT_PER];
@@ -165,7 +245,8 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
     id[u] = -1;
     nx[u] = 0;
     if (i < nc) {
-      if (gin) id[u] = gin[(size_t)b * nc + i];
+      if (gin) id[u] = gin[i];
+      else if (LADDER && started) id[u] = (int32_t)g[i];
       nx[u] = wb[i];                       // row 0 of the matrix, for step 0
       first[i] = 0x7FFFFFFF;
       size[i] = 0;
@@ -193,13 +274,14 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
 
   // ---- Q at the start: this thread's q against every p < q of its slot ----------------------
   long long q_start = 0;
-  if (gin) {                               // uniform; singletons have Q = 0
+  if (started) {                           // uniform; singletons have Q = 0
     for (int p = 0; p < nc - 1; ++p) {
       const int32_t sp = slot[p];
 #pragma unroll
       for (int u = 0; u < UT_PER; ++u) {
         const int q = tid + u * RF_NT;
-        if (q > p && q < nc && my[u] == sp) q_start += wb[(size_t)p * nc + q];
+        if (q > p && q < nc && my[u] == sp)
+          q_start += rf_word_gain<LADDER>(wb[(size_t)p * nc + q], tp);
       }
     }
     q_start = rf_wave_sum64(q_start);
@@ -222,7 +304,7 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
 #pragma unroll
       for (int u = 0; u < UT_PER; ++u) {
         const int q = tid + u * RF_NT;
-        a[u] = nx[u];
+        a[u] = rf_word_gain<LADDER>(nx[u], tp);
         nx[u] = q < nc ? nrow[q] : 0;      // the next step's row
         if (q < nc && q != p && a[u] != 0) atomicAdd(&S[cur][my[u]], a[u]);
       }
@@ -292,14 +374,14 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
   __syncthreads();
   const uint32_t G = ut_label(par, rnk, g, wsum, nc);
 
-  const uint32_t TG = ut_true_groups(par, rnk, t, wsum, ut_label_rows(ybits, b, nc), nc);
+  const uint32_t TG = ut_true_groups(par, rnk, t, wsum, yb, nc);
   ut_pair_counts(g, t, red, nc);
 
   // ---- outputs ------------------------------------------------------------------------------
-  for (int i = tid; i < nc; i += RF_NT) groups[(size_t)b * nc + i] = (int32_t)g[i];
+  if (groups)                              // uniform
+    for (int i = tid; i < nc; i += RF_NT) groups[i] = (int32_t)g[i];
   __syncthreads();
   if (tid == 0) {
-    u64* row = ut + (size_t)b * HDG_RF_SLOTS;
     ut_pair_table(red, G, TG, nc, row);
     u64 nans = 0;
     const uint32_t* cnt = reinterpret_cast<const uint32_t*>(wb) + (size_t)nc * nc;
@@ -307,12 +389,53 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
     for (int f = 0; f < tiles; ++f) nans += cnt[f];
     row[HDG_RF_MOVES] = moves;
     row[HDG_RF_NAN] = nans;
-    long long* qrow = rq + (size_t)b * HDG_RF_Q_SLOTS;
     qrow[HDG_RF_Q_START] = q_start;
     qrow[HDG_RF_Q_END] = q_start + gain;
     qrow[HDG_RF_Q_SWEEPS] = sweeps;
     qrow[HDG_RF_Q_CONVERGED] = converged;
   }
+}
+
+__global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ ws,
+                                                    const uint32_t* __restrict__ ybits,
+                                                    const int32_t* gin, int32_t* groups,
+                                                    u64* __restrict__ ut,
+                                                    long long* __restrict__ rq, const int nc,
+                                                    const int max_sweeps) {
+  const size_t b = blockIdx.x;
+  rf_sweep<false>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+                  gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
+                  ut + b * HDG_RF_SLOTS, rq + b * HDG_RF_Q_SLOTS, nc, max_sweeps);
+}
+
+// grid (rungs, B): the rungs of a commit are dispatched together and share its matrix in L2;
+// outputs [rung][b]
+__global__ __launch_bounds__(RF_NT) void k_rl_sweep(const int32_t* __restrict__ ws,
+                                                    const uint32_t* __restrict__ ybits,
+                                                    const int32_t* __restrict__ merges,
+                                                    const float* __restrict__ levels,
+                                                    const rl_bounds bounds, int32_t* groups,
+                                                    u64* __restrict__ ut,
+                                                    long long* __restrict__ rq, const int nc,
+                                                    const int max_sweeps) {
+  const size_t b = blockIdx.y, o = (size_t)blockIdx.x * gridDim.y + b;
+  const size_t n1 = (size_t)nc - 1;
+  rf_sweep<true>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
+                 merges ? merges + b * n1 * 2 : nullptr, merges ? levels + b * n1 : nullptr,
+                 bounds.tp[blockIdx.x], groups ? groups + o * nc : nullptr,
+                 ut + o * HDG_RF_SLOTS, rq + o * HDG_RF_Q_SLOTS, nc, max_sweeps);
+}
+
+// what hdg_refine and hdg_refine_ladder check first, in this order
+inline int rf_check_call(const hdg_shape* s, const int32_t rule, const int32_t max_sweeps,
+                         const int32_t flags, const char* who) {
+  if (const int rc = ut_check_shape(s, who)) return rc;
+  if (const int rc = ut_check_rule(rule, who)) return rc;
+  if (max_sweeps < 1 || max_sweeps > HDG_RF_MAX_SWEEPS)
+    return fail(HDG_EINVAL, "%s: max_sweeps must be in [1, %d] (got %d)", who, HDG_RF_MAX_SWEEPS,
+                (int)max_sweeps);
+  if (flags != 0) return fail(HDG_EINVAL, "%s: unknown flag bits 0x%x", who, (unsigned)flags);
+  return 0;
 }
 
 }  // namespace
@@ -327,12 +450,7 @@ extern "C" int hdg_refine(const hdg_shape* s, const hdg_batch* bt, const float* 
                           float threshold, int32_t rule, int32_t max_sweeps, int32_t flags,
                           const int32_t* groups_in, int32_t* groups, uint64_t* ut, int64_t* rq,
                           void* workspace, void* stream) {
-  if (const int rc = ut_check_shape(s, "hdg_refine")) return rc;
-  if (const int rc = ut_check_rule(rule, "hdg_refine")) return rc;
-  if (max_sweeps < 1 || max_sweeps > HDG_RF_MAX_SWEEPS)
-    return fail(HDG_EINVAL, "hdg_refine: max_sweeps must be in [1, %d] (got %d)",
-                HDG_RF_MAX_SWEEPS, (int)max_sweeps);
-  if (flags != 0) return fail(HDG_EINVAL, "hdg_refine: unknown flag bits 0x%x", (unsigned)flags);
+  if (const int rc = rf_check_call(s, rule, max_sweeps, flags, "hdg_refine")) return rc;
   const float tp = ut_link_bound(rule, threshold);
   if (!std::isfinite(threshold) || !std::isfinite(tp))
     return fail(HDG_EINVAL, "hdg_refine: threshold %g gives no finite link bound",
@@ -350,4 +468,44 @@ extern "C" int hdg_refine(const hdg_shape* s, const hdg_batch* bt, const float* 
                      (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
                      (long long*)rq, nc, (int)max_sweeps);
   return ut_launched("hdg_refine", "sweep");
+}
+
+extern "C" size_t hdg_refine_ladder_workspace_bytes(const hdg_shape* s, int32_t flags) {
+  if (ut_check_shape(s, "hdg_refine_ladder_workspace_bytes")) return 0;
+  (void)flags;                             // no flag is defined; hdg_refine_ladder rejects any bit
+  return (size_t)s->batch * rf_commit_words(s->nc) * sizeof(int32_t);     // no factor n_rungs
+}
+
+extern "C" int hdg_refine_ladder(const hdg_shape* s, const hdg_batch* bt, const float* probs,
+                                 const float* thresholds, int32_t n_rungs, int32_t rule,
+                                 int32_t max_sweeps, int32_t flags, const int32_t* merges,
+                                 const float* levels, int32_t* groups, uint64_t* ut, int64_t* rq,
+                                 void* workspace, void* stream) {
+  if (const int rc = rf_check_call(s, rule, max_sweeps, flags, "hdg_refine_ladder")) return rc;
+  if (n_rungs < 1 || n_rungs > HDG_RL_MAX_RUNGS)
+    return fail(HDG_EINVAL, "hdg_refine_ladder: n_rungs must be in [1, %d] (got %d)",
+                HDG_RL_MAX_RUNGS, (int)n_rungs);
+  if (!thresholds) return fail(HDG_EINVAL, "hdg_refine_ladder: NULL pointer (thresholds)");
+  rl_bounds bounds = {};
+  for (int k = 0; k < n_rungs; ++k) {      // each rung's t' once, here, as hdg_refine forms it
+    bounds.tp[k] = ut_link_bound(rule, thresholds[k]);
+    if (!std::isfinite(thresholds[k]) || !std::isfinite(bounds.tp[k]))
+      return fail(HDG_EINVAL, "hdg_refine_ladder: rung %d: threshold %g gives no finite link "
+                              "bound", k, (double)thresholds[k]);
+  }
+  if ((merges == nullptr) != (levels == nullptr))
+    return fail(HDG_EINVAL, "hdg_refine_ladder: merges and levels come together or not at all");
+  if (!bt || !bt->ybits || !probs || !ut || !rq || !workspace)
+    return fail(HDG_EINVAL, "hdg_refine_ladder: NULL pointer (batch, batch->ybits, probs, ut, rq "
+                            "or workspace)");
+  if (const int rc = ut_check_workspace(workspace, "hdg_refine_ladder")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int nc = s->nc;
+  hipLaunchKernelGGL(k_rl_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
+                     dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule);
+  if (const int rc = ut_launched("hdg_refine_ladder", "weights")) return rc;
+  hipLaunchKernelGGL(k_rl_sweep, dim3((unsigned)n_rungs, (unsigned)s->batch), dim3(RF_NT), 0, st,
+                     (const int32_t*)workspace, bt->ybits, merges, levels, bounds, groups,
+                     (u64*)ut, (long long*)rq, nc, (int)max_sweeps);
+  return ut_launched("hdg_refine_ladder", "sweep");
 }

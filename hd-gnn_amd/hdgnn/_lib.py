@@ -84,6 +84,8 @@ RF_SLOTS, RF_MOVES, RF_NAN = 8, 6, 7
 RF_Q_SLOTS = 4
 RF_Q_START, RF_Q_END, RF_Q_SWEEPS, RF_Q_CONVERGED = range(4)
 RF_MAX_SWEEPS = 64
+# hdg_refine_ladder: the most rungs one call takes (include/hdgnn.h)
+RL_MAX_RUNGS = 64
 
 
 def untangle_blocks(nc):
@@ -111,7 +113,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_eval", "hdg_untangle_workspace_bytes", "hdg_untangle",
            "hdg_linkage_workspace_bytes", "hdg_linkage",
            "hdg_agglomerate_workspace_bytes", "hdg_agglomerate", "hdg_cut",
-           "hdg_refine_workspace_bytes", "hdg_refine"]
+           "hdg_refine_workspace_bytes", "hdg_refine",
+           "hdg_refine_ladder_workspace_bytes", "hdg_refine_ladder"]
 
 _lib = None
 
@@ -165,6 +168,10 @@ def load(path=None):
     lib.hdg_refine_workspace_bytes.argtypes = [P(Shape), i32]
     lib.hdg_refine_workspace_bytes.restype = ctypes.c_size_t
     lib.hdg_refine.argtypes = [P(Shape), P(Batch), vp, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.hdg_refine_ladder_workspace_bytes.argtypes = [P(Shape), i32]
+    lib.hdg_refine_ladder_workspace_bytes.restype = ctypes.c_size_t
+    lib.hdg_refine_ladder.argtypes = [P(Shape), P(Batch), vp, P(f32), i32, i32, i32, i32, vp, vp,
+                                      vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

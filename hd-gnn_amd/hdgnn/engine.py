@@ -9,6 +9,7 @@ every rank is on this node, else torch.distributed (RCCL); HDG_DP_ALLREDUCE or t
 `allreduce` argument ("auto" | "xgmi" | "rccl") overrides the choice.
 """
 import ctypes
+import math
 import os
 import warnings
 
@@ -569,3 +570,59 @@ class Engine:
                                        ctypes.c_void_p(ws.data_ptr()),
                                        self._stream()))
         return out, ut, rq
+
+    def refine_ladder(self, dbatch, thresholds, tree=None, probs=None, rule="mean", max_sweeps=8,
+                      groups=False):
+        """hdg_refine_ladder: refine() at every one of the T `thresholds` (a host sequence of 1
+        to RL_MAX_RUNGS finite floats, in any order) in one call, rung k starting from the cut
+        at thresholds[k] of `tree` = (merges, levels) as linkage() or agglomerate() returned
+        them (None: every hunk alone) -> (ut int64 [T][B][RF_SLOTS], rq int64
+        [T][B][RF_Q_SLOTS], groups int32 [T][B][nc] or None unless `groups`) as fresh device
+        tensors: rung k holds what cut() then refine() at thresholds[k] return
+        (hdgnn.metrics.best_rung picks the rung).  `probs` as untangle()'s.  Enqueued on the
+        current stream; nothing is copied to the host; a captured graph replays the captured
+        thresholds.  The workspace is allocated on the first call and kept."""
+        self._check(dbatch)
+        probs = self._decode_probs(probs)
+        rule = self._rule(rule)
+        if not (isinstance(max_sweeps, int) and 1 <= max_sweeps <= _lib.RF_MAX_SWEEPS):
+            raise ValueError("max_sweeps must be an int in [1, %d] (got %r)"
+                             % (_lib.RF_MAX_SWEEPS, max_sweeps))
+        try:
+            thr = [float(t) for t in thresholds]
+        except TypeError:
+            raise ValueError("thresholds must be a sequence of floats (got %r)" % (thresholds,))
+        if not 1 <= len(thr) <= _lib.RL_MAX_RUNGS or not all(math.isfinite(t) for t in thr):
+            raise ValueError("thresholds must be 1 to %d finite floats (got %r)"
+                             % (_lib.RL_MAX_RUNGS, thr))
+        merges = levels = None
+        if tree is not None:
+            n1 = self.nc - 1
+            try:
+                merges, levels = tree
+            except (TypeError, ValueError):
+                raise ValueError("tree must be (merges, levels)")
+            for x, dt, shp in ((merges, torch.int32, (self.batch, n1, 2)),
+                               (levels, torch.float32, (self.batch, n1))):
+                if (not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != dt
+                        or not x.is_contiguous() or tuple(x.shape) != shp):
+                    raise ValueError("tree must be the contiguous (merges, levels) linkage() / "
+                                     "agglomerate() return for this engine")
+        ws = self._workspace("_rl_workspace", lambda: self.lib.hdg_refine_ladder_workspace_bytes(
+            ctypes.byref(self.shape), 0), torch.int64)
+        T = len(thr)
+        out = (torch.empty(T, self.batch, self.nc, dtype=torch.int32, device=self.device)
+               if groups else None)
+        # u64 counts, every value < 2^63: int64 reads them as they are
+        ut = torch.empty(T, self.batch, _lib.RF_SLOTS, dtype=torch.int64, device=self.device)
+        rq = torch.empty(T, self.batch, _lib.RF_Q_SLOTS, dtype=torch.int64, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_refine_ladder(
+            ctypes.byref(self.shape), ctypes.byref(b), ctypes.c_void_p(probs.data_ptr()),
+            (ctypes.c_float * T)(*thr), T, rule, max_sweeps, 0,
+            None if merges is None else ctypes.c_void_p(merges.data_ptr()),
+            None if levels is None else ctypes.c_void_p(levels.data_ptr()),
+            None if out is None else ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(ut.data_ptr()), ctypes.c_void_p(rq.data_ptr()),
+            ctypes.c_void_p(ws.data_ptr()), self._stream()))
+        return ut, rq, out

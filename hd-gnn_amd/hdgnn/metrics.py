@@ -688,3 +688,69 @@ def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8
                  np.count_nonzero(~sp & ~st), moves, nans)
         rq[b] = (q0, q1, sweeps, conv)
     return ut, out, rq
+
+
+# ---------------------------------------------------------------------------------------
+# Refinement ladder: refine at every rung of a ladder of thresholds, each rung from the cut
+# of a merge tree at that rung, as hdg_refine_ladder runs it on the device (include/hdgnn.h,
+# HDG_RL_*), its host restatement, and the rung with the best pooled score -- the threshold
+# calibrated for the refined result, which is not the tree's best cut.
+# ---------------------------------------------------------------------------------------
+RL_MAX_RUNGS = 64
+
+
+def ladder(lo, hi, n):
+    """The n rungs float32(lo + (hi - lo) k / (n - 1)), k = 0 .. n-1, the arithmetic in
+    float64; n == 1 gives lo.  1 <= n <= RL_MAX_RUNGS, finite ends."""
+    if not (isinstance(n, (int, np.integer)) and not isinstance(n, bool)
+            and 1 <= n <= RL_MAX_RUNGS):
+        raise ValueError("a ladder has 1 to %d rungs (got %r)" % (RL_MAX_RUNGS, n))
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("a ladder's ends must be finite (got %r, %r)" % (lo, hi))
+    if n == 1:
+        return np.array([lo], np.float32)
+    return (lo + (hi - lo) * np.arange(n, dtype=np.float64) / (n - 1)).astype(np.float32)
+
+
+def _rungs(thresholds):
+    thr = np.asarray(thresholds, np.float32).reshape(-1)
+    if not 1 <= len(thr) <= RL_MAX_RUNGS:
+        raise ValueError("a ladder has 1 to %d rungs (got %d)" % (RL_MAX_RUNGS, len(thr)))
+    return thr
+
+
+def refine_ladder(label_onehot, probs, thresholds, tree=None, rule="mean", max_sweeps=8):
+    """(B, 2, R) one-hot labels and probabilities, T thresholds and tree = (merges, levels) of
+    any merge tree or None -> (ut int64 (T, B, RF_SLOTS), groups int32 (T, B, Nc), rq int64
+    (T, B, RF_Q_SLOTS)): the host restatement of hdg_refine_ladder.  A loop: per rung
+    cut_groups at the rung's link bound (None: every hunk alone), then refine at the rung."""
+    thr = _rungs(thresholds)
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    out = []
+    for t in thr:
+        start = None
+        if tree is not None:
+            with np.errstate(over="ignore"):
+                start = cut_groups(tree[0], tree[1], t + t if rule == "mean" else t)
+        out.append(refine(label_onehot, probs, start, t, rule, max_sweeps))
+    return tuple(np.stack([o[i] for o in out]) for i in range(3))
+
+
+def best_rung(ut_ladder, thresholds, score="f1"):
+    """ut_ladder int (T, n_commits, RF_SLOTS) and the T thresholds -> (index, threshold, score,
+    per-rung scores float64 (T,)): the rung with the best pooled `score` ("f1" | "rand",
+    scores_from_untangle's) over the commits.  A nan score never wins; ties go to the lowest
+    index; if every score is nan: index 0, with a nan score."""
+    if score not in ("f1", "rand"):
+        raise ValueError("score must be 'f1' or 'rand' (got %r)" % (score,))
+    thr = _rungs(thresholds)
+    ut = np.asarray(ut_ladder)
+    if ut.shape[0] != len(thr) or ut.shape[-1] != RF_SLOTS:
+        raise ValueError("ut_ladder must be (%d, n_commits, %d) (got %r)"
+                         % (len(thr), RF_SLOTS, ut.shape))
+    vals = np.array([scores_from_untangle(ut[k])[score] for k in range(len(thr))], np.float64)
+    good = ~np.isnan(vals)
+    i = int(np.flatnonzero(good & (vals == vals[good].max()))[0]) if good.any() else 0
+    return i, float(thr[i]), float(vals[i]), vals

@@ -750,6 +750,94 @@ class graph2graph(object):
             print('calibrate threshold: %r (link bound %r)' % (threshold, tprime))
         return threshold, scores, levels, curve, lk
 
+    # ------------------------------------------------------------------ calibrate_refined
+    def calibrate_refined(self, args, part="train", rule="mean", score="f1", method="single",
+                          refine=8, ladder=(0.05, 0.95, 19)):
+        """The link threshold untangle(refine=N) should use: the rung of `ladder` = (lo, hi, n)
+        (metrics.ladder) with the best pooled `score` of the REFINED groups over the commits of
+        the train (or test) split -- the objective's threshold is not the tree's best cut,
+        which calibrate() returns.  Per batch Engine.forward, then the merge tree as
+        calibrate() builds it (Engine.linkage, or Engine.agglomerate under `method`), then
+        Engine.refine_ladder from that tree (hdg_refine_ladder: every rung cut from the tree
+        and refined with at most `refine` sweeps, in one call); only the integer rows of each
+        commit and rung and the trees come to the host.  Checkpoint, batches and multi-rank
+        gather as untangle().  -> (threshold, scores dict at it (metrics.scores_from_untangle
+        of that rung's table), thresholds float32 [T], table int64 [T][n_commits][8], rq int64
+        [T][n_commits][4]); rank 0 prints one line per rung, the chosen rung and the tree's
+        own best (metrics.best_threshold on the same trees) beside it, and writes
+        refine_ladder_thresholds<Ne>.npy, refine_ladder_counts<Ne>.npy and
+        refine_ladder_objective<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/."""
+        import torch
+        if part not in ("train", "test"):
+            raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
+        if method not in _lib.AG_METHODS:
+            raise ValueError("method must be one of %s (got %r)"
+                             % (", ".join(_lib.AG_METHODS), method))
+        if not (isinstance(refine, int) and 1 <= refine <= _lib.RF_MAX_SWEEPS):
+            raise ValueError("refine must be an int in [1, %d] (got %r)"
+                             % (_lib.RF_MAX_SWEEPS, refine))
+        thresholds = metrics.ladder(*ladder)
+        T = len(thresholds)
+        _, _, train, test, maps = self._compact()
+        if self.load(self.checkpoint_dir):
+            print(" [*] Load SUCCESS")
+        else:
+            print(" [!] Load failed...")
+        eng = self.engine
+        outs = []
+        for db in self._device_batches(train if part == "train" else test, maps):
+            eng.forward(db)
+            m, lv, cv, _, lk = (eng.linkage(db, rule=rule) if method == "single"
+                                else eng.agglomerate(db, rule=rule, method=method))
+            ut, rq, _ = eng.refine_ladder(db, thresholds.tolist(), tree=(m, lv), rule=rule,
+                                          max_sweeps=refine)
+            # batch-major like the tree's arrays, the rungs inside: [lb][T][slots]
+            outs.append((lv, cv, lk, ut.transpose(0, 1).contiguous(),
+                         rq.transpose(0, 1).contiguous()))
+        nb, lb, n1 = len(outs), self.local_batch, self.Nc - 1
+        tails = ((n1,), (n1, 2), (_lib.LK_SLOTS,), (T, _lib.RF_SLOTS), (T, _lib.RF_Q_SLOTS))
+        dtypes = (np.float32, np.int32, np.int64, np.int64, np.int64)
+        arrs = [(torch.stack([o[i] for o in outs]).cpu().numpy() if nb
+                 else np.zeros((0, lb) + tails[i], dtypes[i])) for i in range(5)]
+        eng.check_status()
+        if self.world > 1 and nb:      # rank-major (W nb, lb, ..) -> batch-major commit order
+            arrs = [self._gather(a).reshape((self.world, nb, lb) + tails[i])
+                    .transpose((1, 0, 2) + tuple(range(3, 3 + len(tails[i]))))
+                    for i, a in enumerate(arrs)]
+        levels, curve, lk, table, qrows = (np.ascontiguousarray(a.reshape((-1,) + tails[i]))
+                                           for i, a in enumerate(arrs))
+        curve, lk = curve.astype(np.int64), lk.astype(np.int64)
+        table = np.ascontiguousarray(table.transpose(1, 0, 2)).astype(np.int64)    # [T][n][8]
+        qrows = np.ascontiguousarray(qrows.transpose(1, 0, 2)).astype(np.int64)
+        k, threshold, best, vals = metrics.best_rung(table, thresholds, score)
+        scores = metrics.scores_from_untangle(table[k])
+        tree_thr, tree_best, _ = metrics.best_threshold(levels, curve, lk, rule, score)
+        if self.rank == 0:
+            step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
+            os.makedirs(step_dir, exist_ok=True)
+            np.save(step_dir + 'refine_ladder_thresholds' + str(self.Ne) + '.npy', thresholds)
+            np.save(step_dir + 'refine_ladder_counts' + str(self.Ne) + '.npy', table)
+            np.save(step_dir + 'refine_ladder_objective' + str(self.Ne) + '.npy', qrows)
+            n = table.shape[1]
+            print('calibrate refined rule: %s, part %s (%d commits), method %s, %d sweeps at most'
+                  % (rule, part, n, method, refine))
+            for j in range(T):
+                print('calibrate refined rung %d: threshold %r, %s = %s, %d moves, %d of %d '
+                      'commits converged'
+                      % (j, float(thresholds[j]), score, vals[j],
+                         int(table[j, :, _lib.RF_MOVES].sum()),
+                         int(qrows[j, :, _lib.RF_Q_CONVERGED].sum()), n))
+            print('calibrate refined threshold: %r (rung %d), %s = %s' % (threshold, k, score, best))
+            print('calibrate refined tree alone: threshold %r, %s = %s' % (tree_thr, score,
+                                                                          tree_best))
+            if best > tree_best:
+                print('calibrate refined: the refined rung scores higher than the tree alone')
+            elif tree_best > best:
+                print('calibrate refined: the tree alone scores higher than every refined rung')
+            else:
+                print('calibrate refined: neither scores higher (equal, or no score defined)')
+        return threshold, scores, thresholds, table, qrows
+
     # ------------------------------------------------------------------ test
     def test(self, args):
         _, C_edge_test, _, test, maps = self._compact()

@@ -18,6 +18,11 @@ MI355X instead of a TF1 session.
                                                # groups from complete / average linkage trees
     python hd-gnn_amd/main.py --Type untangle --link-method average --link-refine 8
                                                # ... then up to 8 best-move sweeps over them
+    python hd-gnn_amd/main.py --Type untangle --link-threshold refined --link-refine 8 \\
+        [--link-ladder 0.05:0.95:19]           # ... at the threshold calibrated for the REFINED
+                                               # groups: the best rung of the ladder LO:HI:N
+    python hd-gnn_amd/main.py --Type calibrate --link-threshold refined --link-refine 8
+                                               # that threshold alone (one ladder call per batch)
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -40,7 +45,21 @@ def _init_distributed():
 
 
 def _threshold(text):
-    return text if text == 'auto' else float(text)
+    return text if text in ('auto', 'refined') else float(text)
+
+
+def _ladder(text):
+    """LO:HI:N -> (lo, hi, n), checked as hdgnn.metrics.ladder checks it."""
+    import math
+    try:
+        lo, hi, n = text.split(':')
+        lo, hi, n = float(lo), float(hi), int(n)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected LO:HI:N (got %r)" % (text,))
+    if not (math.isfinite(lo) and math.isfinite(hi) and 1 <= n <= 64):
+        raise argparse.ArgumentTypeError("LO:HI:N needs finite ends and 1 <= N <= 64 (got %r)"
+                                         % (text,))
+    return lo, hi, n
 
 
 def _variant(argv):
@@ -56,7 +75,12 @@ def _variant(argv):
     graph's components): the linkage whose merge tree both cut (hdg_agglomerate, hdg_cut);
     --link-refine N (default 0: none): --Type untangle passes its groups through at most N
     best-move sweeps (hdg_refine) at the same threshold and rule -- with --link-threshold auto
-    the one calibrated for the tree; --Type calibrate does not look at it."""
+    the one calibrated for the tree; --Type calibrate does not look at it, except with
+    --link-threshold refined: the threshold with the best pooled --link-score of the groups
+    REFINED with at most --link-refine N sweeps (N >= 1 is required), among the rungs of
+    --link-ladder LO:HI:N (default 0.05:0.95:19), every rung cut from the commits' merge trees
+    and refined in one call (hdg_refine_ladder); --Type calibrate computes it alone, --Type
+    untangle uses it."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
@@ -65,7 +89,10 @@ def _variant(argv):
     p.add_argument('--link-score', default='f1', choices=('f1', 'rand'))
     p.add_argument('--link-method', default='single', choices=('single', 'complete', 'average'))
     p.add_argument('--link-refine', type=int, default=0)
+    p.add_argument('--link-ladder', type=_ladder, default=(0.05, 0.95, 19))
     a, rest = p.parse_known_args(argv)
+    if a.link_threshold == 'refined' and a.link_refine < 1:
+        p.error("--link-threshold refined needs --link-refine N with N >= 1")
     return a, rest
 
 
@@ -138,17 +165,25 @@ def main(argv=None, model_cls=None):
             model.evaluate(args)
         # single linkage is the call as it always was; another method is passed on
         how = {} if extra.link_method == 'single' else {'method': extra.link_method}
+        # the threshold calibrated for the refined groups: the best rung of the ladder
+        refined = dict(rule=extra.link_rule, score=extra.link_score, refine=extra.link_refine,
+                       ladder=extra.link_ladder, **how)
         if args.Type == 'untangle':  # not in the reference: hunk groups per commit, on the device
             threshold = extra.link_threshold
-            if threshold == 'auto':
+            if threshold == 'refined':
+                threshold = model.calibrate_refined(args, part="train", **refined)[0]
+            elif threshold == 'auto':
                 threshold = model.calibrate(args, part="train", rule=extra.link_rule,
                                             score=extra.link_score, **how)[0]
             # without refinement the call is the one it always was
             more = {'refine': extra.link_refine} if extra.link_refine else {}
             model.untangle(args, threshold=threshold, rule=extra.link_rule, **how, **more)
         if args.Type == 'calibrate':  # not in the reference: the best link threshold, on the device
-            model.calibrate(args, part="train", rule=extra.link_rule, score=extra.link_score,
-                            **how)
+            if extra.link_threshold == 'refined':
+                model.calibrate_refined(args, part="train", **refined)
+            else:
+                model.calibrate(args, part="train", rule=extra.link_rule, score=extra.link_score,
+                                **how)
 
 
 if __name__ == '__main__':

@@ -19,7 +19,8 @@
  * Conventions
  *   - every pointer is a caller-owned DEVICE pointer (the library never allocates);
  *     `stream` is a hipStream_t passed as void*; all work is enqueued on it, no host
- *     synchronisation happens inside any call (graph-capturable).
+ *     synchronisation happens inside any call (graph-capturable).  The one exception:
+ *     hdg_refine_ladder's `thresholds` is a HOST array, read during the call only.
  *   - return 0 on success, HDG_EINVAL for a shape/argument error, or the hipError_t
  *     of a failed launch; hdg_last_error() gives a thread-local message.
  *   - parameters are one flat fp32 vector in tf.global_variables() order with TF
@@ -559,6 +560,55 @@ int    hdg_refine(const hdg_shape* shape, const hdg_batch* batch, const float* p
                   uint64_t* ut             /* [batch][HDG_RF_SLOTS] */,
                   int64_t* rq              /* [batch][HDG_RF_Q_SLOTS] */,
                   void* workspace, void* stream);
+
+/* hdg_refine_ladder: hdg_refine at every rung of a ladder of thresholds in one call, each
+ * rung starting from the cut of a merge tree at that rung -- what calibrating a threshold for
+ * the refined result needs (hdgnn.metrics.refine_ladder restates it, metrics.best_rung picks).
+ *
+ *   thresholds  a HOST array of n_rungs floats, n_rungs in [1, HDG_RL_MAX_RUNGS]: the one
+ *            argument of this header that is not a device pointer.  It is read during the
+ *            call only; each rung's t' is formed once on the host exactly as hdg_refine forms
+ *            it, and the bounds travel to the kernel as a by-value argument.  Rungs need not be
+ *            sorted or distinct; each threshold and each t' must be finite
+ *   start    with merges ([batch][nc-1][2]) and levels ([batch][nc-1]) of hdg_linkage or
+ *            hdg_agglomerate given, rung k starts from the groups hdg_cut gives on that tree
+ *            at thresholds[k] under `rule` (the merges with level > t' united, rows of -1 /
+ *            NaN skipped); with both NULL every hunk starts alone, as hdg_refine with
+ *            groups_in NULL.  One without the other is an error
+ *   outputs  rung k of groups ([n_rungs][batch][nc], or NULL: not stored), ut
+ *            ([n_rungs][batch][HDG_RF_SLOTS]) and rq ([n_rungs][batch][HDG_RF_Q_SLOTS]) holds,
+ *            integer for integer and slot for slot, what hdg_cut(merges, levels,
+ *            thresholds[k], rule) followed by hdg_refine(thresholds[k], rule, max_sweeps,
+ *            groups_in = those groups) writes -- or hdg_refine with groups_in NULL without a
+ *            tree.  Weights, pairs that are no edge, gains, tie rules, sweep order, stop rule
+ *            and every slot are hdg_refine's, above
+ *   workspace  hdg_refine_ladder_workspace_bytes(shape, flags) bytes, hdg_refine's size
+ *            whatever n_rungs is, 8-byte aligned; its content before the call does not matter
+ * Every slot of every rung is written by the call.  Two launches on `stream`: k_rl_weights is
+ * k_rf_weights storing the fp32 weight of every pair (one canonical NaN for a pair that is no
+ * edge and on the diagonal) instead of its gain at one bound; the sweep kernel runs
+ * k_rf_sweep's block on a grid (n_rungs, batch), forming a_pq from the stored weight and its
+ * rung's t' with hdg_refine's own expression -- the same function of the same w, so no new
+ * rounding -- after uniting the tree's merges above t' in LDS as hdg_cut does.  The call
+ * allocates nothing, does not synchronise, no block waits for another; it is graph-capturable,
+ * and a captured graph replays the captured ladder (the bounds are part of the launch).  The
+ * sweep loop is bounded by max_sweeps, the step loop by nc, the unions by nc - 1.  HDG_EINVAL
+ * (the message starts "hdg_refine_ladder:"; nothing is launched) for everything hdg_refine
+ * rejects except a NULL groups, n_rungs out of range, a NULL thresholds, a rung whose
+ * threshold or t' is not finite (the message names the rung), exactly one of merges and
+ * levels, or any flag bit.                                                                */
+#define HDG_RL_MAX_RUNGS 64
+
+size_t hdg_refine_ladder_workspace_bytes(const hdg_shape* shape, int32_t flags);   /* 0 on a shape error */
+int    hdg_refine_ladder(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                         const float* thresholds /* HOST, [n_rungs] */, int32_t n_rungs,
+                         int32_t rule, int32_t max_sweeps, int32_t flags,
+                         const int32_t* merges /* [batch][nc-1][2] or NULL */,
+                         const float* levels   /* [batch][nc-1]    or NULL */,
+                         int32_t* groups  /* [n_rungs][batch][nc] or NULL */,
+                         uint64_t* ut     /* [n_rungs][batch][HDG_RF_SLOTS] */,
+                         int64_t* rq      /* [n_rungs][batch][HDG_RF_Q_SLOTS] */,
+                         void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
