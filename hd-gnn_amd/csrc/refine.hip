@@ -40,6 +40,29 @@
 //                 start is the tree's cut at the rung: k_cut's unions (ut_union, levels > t'
 //                 strictly, rows of -1 / NaN skipped) and ut_label in the LDS arrays of the
 //                 sums, which are free before the sweeps; bounded by nc - 1.
+//
+// hdg_refine_merge and hdg_refine_merge_ladder are those sweep blocks with rounds
+// (rf_sweep<LADDER, MERGE = true>, k_rm_sweep and k_rml_sweep; the weights launches are the two
+// above): a round is the node phase -- the sweeps above, unchanged -- and one group sweep, which
+// lets two whole groups merge.  A group sweep inside the block:
+//   chains   once per group sweep every slot's members are chained through first (a slot's
+//            head), g (a member's successor) and t (a slot's tail), which are free between the
+//            start and the final labelling: one LDS exchange per hunk.  A merge appends one
+//            chain to another in O(1) (thread 0).  The order of a chain does not matter: every
+//            sum is an integer.
+//   visit g  every thread sums a_pq over the members p of g for its own hunks q in registers
+//            (int32: at most UT_MAXN - 1 members), reading the members' rows from the workspace
+//            one member ahead; no barrier between rows.  Then C[h] = sum of c_q over q in h by
+//            two int32 LDS atomics on a 16-bit split of c_q (low parts into S[0], high parts
+//            into S[1]: exact, UT_MAXN * 2^16 < 2^31); barrier; every owner of a non-empty slot
+//            h != g offers rm_key(C[h], h) and zeroes its two sums, wave maxima by rf_wave_max;
+//            barrier; every thread reaches the same decision and rewrites its own hunks' slots,
+//            thread 0 the sizes and the chain.  Two barriers per non-empty slot, none for an
+//            empty one: what thread 0 writes after a merge belongs to slots min(g, h) <= g
+//            and max(g, h), and the visits up to the next barrier read neither (the emptied
+//            slot is skipped from a register).
+// The round loop is bounded by max_rounds, a group sweep's visits by nc, a chain walk by the
+// slot's size, the total of node sweeps by max_sweeps.
 // Integer results only; the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -59,6 +82,12 @@ constexpr float RF_SCALE = 262144.f;         // 2^18: a = rint(d * 2^18), |a| <=
 static_assert(RF_NT * UT_PER == UT_MAXN, "a thread owns UT_PER hunks and slots");
 static_assert((UT_MAXN - 1) * (1ll << 19) < (1ll << 31), "a node sum fits int32");
 static_assert(UT_MAXN <= 2048, "the key's tie field holds two ranges of 2048 slots");
+// a group sweep (hdg_refine_merge): the gain of a merge and its key, the 16-bit split
+static_assert((long long)(UT_MAXN / 2) * (UT_MAXN / 2) * (1ll << 19) <= (1ll << 39),
+              "a merge gain is at most 2^39 in magnitude");
+static_assert(UT_MAXN <= (1 << 11), "the merge key's tie field holds 11 bits of slot");
+static_assert(41 + 11 <= 64, "the biased merge gain (below 2^41) and the tie field fit one key");
+static_assert((long long)UT_MAXN * (1ll << 16) < (1ll << 31), "a slot's sum of 16-bit parts fits int32");
 
 // workspace, in 4-byte words per commit: the nc x nc matrix of gains, then ut_tiles(nc)
 // no-edge counts, rounded up to an even number of words
@@ -151,6 +180,13 @@ __device__ __forceinline__ u64 rf_key(const int32_t v, const bool empty, const i
   return ((u64)((uint32_t)v ^ 0x80000000u) << 12) | (u64)((empty ? 0 : 2048) + (2047 - h));
 }
 
+// a candidate of a group visit as one key: the larger key wins.  The gain C (|C| <= 2^39,
+// biased by 2^40: never 0), then the lower slot.  0 is no candidate.
+constexpr long long RM_BIAS = 1ll << 40;
+__device__ __forceinline__ u64 rm_key(const long long c, const int h) {
+  return ((u64)(c + RM_BIAS) << 11) | (u64)(2047 - h);
+}
+
 // max(k, the key CTRL brings from another lane); a lane without a source, or in a row ROWS
 // masks out, gets 0, the identity
 template <int CTRL, int ROWS>
@@ -193,19 +229,138 @@ __device__ __forceinline__ int32_t rf_word_gain(const int32_t word, const float 
   return w != w ? 0 : rf_gain(w, tp);
 }
 
+// One group sweep of hdg_refine_merge inside the sweep block (the header's definition; the
+// steps at the top of this file), after a node phase: the last step's move is not yet behind
+// a barrier, S[cur] is zero and the other buffer is not.  head, next and tail are the block's
+// first, g and t.  my: this thread's hunks' slots, rewritten by a merge.  -> the merges made,
+// uniform; their gains are added to `gain`.  On return both buffers of S are zero and every
+// write is behind a barrier.
+template <bool LADDER>
+__device__ __forceinline__ uint32_t rm_group_sweep(const int32_t* __restrict__ wb, const float tp,
+                                                   const int nc, const int nwav,
+                                                   int32_t (*S)[UT_MAXN], int32_t* slot,
+                                                   int32_t* size, int32_t* head, uint32_t* next,
+                                                   uint32_t* tail, u64* wkey,
+                                                   int32_t (&my)[UT_PER], long long& gain) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < UT_PER; ++u) {
+    const int i = tid + u * RF_NT;
+    if (i < nc) {
+      head[i] = -1;
+      S[0][i] = S[1][i] = 0;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < UT_PER; ++u) {       // a slot's chain: the last to arrive is its head,
+    const int i = tid + u * RF_NT;         // the first its tail
+    if (i < nc) {
+      const int32_t old = atomicExch(&head[my[u]], i);
+      next[i] = (uint32_t)old;
+      if (old < 0) tail[my[u]] = (uint32_t)i;
+    }
+  }
+  __syncthreads();
+
+  uint32_t merged = 0;
+  int emptied = -1;                        // the slot the last merge emptied: its size may not
+  for (int gv = 0; gv < nc; ++gv) {        // be behind a barrier yet
+    const int sz = size[gv];
+    if (sz <= 0 || gv == emptied) continue;                 // uniform
+    // c_q = the sum of a_pq over the members p of gv, for this thread's q
+    int32_t c[UT_PER], pre[UT_PER];
+    uint32_t m = (uint32_t)head[gv];
+#pragma unroll
+    for (int u = 0; u < UT_PER; ++u) {
+      const int q = tid + u * RF_NT;
+      c[u] = 0;
+      pre[u] = (m < (uint32_t)nc && q < nc) ? wb[(size_t)m * nc + q] : 0;
+    }
+    for (int k = 0; k < sz && m < (uint32_t)nc; ++k) {      // sz <= nc: a chain cannot spin
+      const uint32_t mn = next[m];
+      const bool more = k + 1 < sz && mn < (uint32_t)nc;
+#pragma unroll
+      for (int u = 0; u < UT_PER; ++u) {
+        const int q = tid + u * RF_NT;
+        c[u] += rf_word_gain<LADDER>(pre[u], tp);
+        pre[u] = (more && q < nc) ? wb[(size_t)mn * nc + q] : 0;      // the next member's row
+      }
+      m = mn;
+    }
+    // C[h] = the sum of c_q over q in h: low 16 bits into S[0], the rest into S[1]
+#pragma unroll
+    for (int u = 0; u < UT_PER; ++u) {
+      const int q = tid + u * RF_NT;
+      if (q < nc && my[u] != gv && c[u] != 0) {
+        atomicAdd(&S[0][my[u]], c[u] & 0xFFFF);
+        atomicAdd(&S[1][my[u]], c[u] >> 16);
+      }
+    }
+    __syncthreads();
+    if (wave < nwav) {
+      u64 key = 0;
+#pragma unroll
+      for (int u = 0; u < UT_PER; ++u) {
+        const int h = tid + u * RF_NT;
+        if (h < nc) {
+          if (h != gv && size[h] > 0) {
+            const u64 k = rm_key((long long)S[1][h] * 65536 + (long long)S[0][h], h);
+            key = k > key ? k : key;
+          }
+          S[0][h] = S[1][h] = 0;           // for the next visit
+        }
+      }
+      key = rf_wave_max(key);
+      if (lane == 63) wkey[wave] = key;
+    }
+    __syncthreads();
+    u64 best = 0;
+    for (int w = 0; w < nwav; ++w) best = wkey[w] > best ? wkey[w] : best;
+    const long long val = (long long)(best >> 11) - RM_BIAS;
+    if (best != 0 && val > 0) {            // uniform: every thread holds the same decision
+      const int h = 2047 - (int)(best & 2047u);
+      const int to = h < gv ? h : gv, from = h < gv ? gv : h;
+#pragma unroll
+      for (int u = 0; u < UT_PER; ++u) {
+        const int i = tid + u * RF_NT;
+        if (i < nc && my[u] == from) {
+          my[u] = to;
+          slot[i] = to;
+        }
+      }
+      if (tid == 0) {                      // the chain of `from` goes behind the chain of `to`
+        const uint32_t end = tail[to];
+        if (end < (uint32_t)nc) next[end] = (uint32_t)head[from];
+        tail[to] = tail[from];
+        size[to] += size[from];
+        size[from] = 0;
+      }
+      emptied = from;
+      ++merged;
+      gain += val;
+    }
+  }
+  __syncthreads();
+  return merged;
+}
+
 // The sweep block of both entry points, on one commit (and one rung): wb its matrix, yb its
 // label rows, and groups (or NULL), row and qrow where its outputs go.  The start is gin, the
 // commit's ids (or NULL) -- or with LADDER the cut of the commit's tree (merges, levels; or
 // NULL) at tp, k_cut's unions.  gin and groups may be the same array: a commit's ids are all
 // read before the first barrier and written after the last.
-template <bool LADDER>
+// With MERGE the sweeps are hdg_refine_merge's rounds (at most max_rounds; a node phase, then
+// one group sweep) and qrow has HDG_RM_Q_SLOTS slots; without it max_rounds is not read.
+template <bool LADDER, bool MERGE>
 __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
                                          const uint32_t* __restrict__ yb, const int32_t* gin,
                                          const int32_t* __restrict__ merges,
                                          const float* __restrict__ levels, const float tp,
                                          int32_t* groups, u64* __restrict__ row,
                                          long long* __restrict__ qrow, const int nc,
-                                         const int max_sweeps) {
+                                         const int max_sweeps, const int max_rounds) {
   __shared__ int32_t S[2][UT_MAXN];        // the per-slot sums of this step and the next
   __shared__ int32_t slot[UT_MAXN];
   __shared__ int32_t size[UT_MAXN];
@@ -296,6 +451,9 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
   int cur = 0, sweeps = 0, converged = 0;
   uint32_t moves = 0;
   long long gain = 0;
+  int rounds = 0;                          // MERGE: group sweeps run, their merges, and the
+  uint32_t nmerged = 0;                    // gain of the first node phase
+  long long node_gain = 0;
   for (int sw = 0; sw < max_sweeps; ++sw) {
     bool moved = false;
     for (int p = 0; p < nc; ++p) {
@@ -356,7 +514,16 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
       cur ^= 1;
     }
     ++sweeps;
-    if (!moved) {
+    if constexpr (MERGE) {                 // a node phase ends here: one group sweep, a round
+      if (moved && sweeps < max_sweeps) continue;
+      if (rounds == 0) node_gain = gain;
+      const uint32_t merged =
+          rm_group_sweep<LADDER>(wb, tp, nc, nwav, S, slot, size, first, g, t, wkey, my, gain);
+      nmerged += merged;
+      ++rounds;
+      converged = !moved && merged == 0;
+      if (merged == 0 || rounds >= max_rounds) break;      // or the sweeps are used up
+    } else if (!moved) {
       converged = 1;
       break;
     }
@@ -393,6 +560,12 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
     qrow[HDG_RF_Q_END] = q_start + gain;
     qrow[HDG_RF_Q_SWEEPS] = sweeps;
     qrow[HDG_RF_Q_CONVERGED] = converged;
+    if constexpr (MERGE) {
+      qrow[HDG_RM_Q_ROUNDS] = rounds;
+      qrow[HDG_RM_Q_MERGES] = nmerged;
+      qrow[HDG_RM_Q_NODE] = q_start + node_gain;
+      qrow[HDG_RM_Q_SLOTS - 1] = 0;
+    }
   }
 }
 
@@ -403,9 +576,23 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
                                                     long long* __restrict__ rq, const int nc,
                                                     const int max_sweeps) {
   const size_t b = blockIdx.x;
-  rf_sweep<false>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
-                  gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
-                  ut + b * HDG_RF_SLOTS, rq + b * HDG_RF_Q_SLOTS, nc, max_sweeps);
+  rf_sweep<false, false>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+                         gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
+                         ut + b * HDG_RF_SLOTS, rq + b * HDG_RF_Q_SLOTS, nc, max_sweeps, 1);
+}
+
+// hdg_refine_merge: k_rf_sweep's block with rounds; rq rows of HDG_RM_Q_SLOTS
+__global__ __launch_bounds__(RF_NT) void k_rm_sweep(const int32_t* __restrict__ ws,
+                                                    const uint32_t* __restrict__ ybits,
+                                                    const int32_t* gin, int32_t* groups,
+                                                    u64* __restrict__ ut,
+                                                    long long* __restrict__ rq, const int nc,
+                                                    const int max_sweeps, const int max_rounds) {
+  const size_t b = blockIdx.x;
+  rf_sweep<false, true>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+                        gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
+                        ut + b * HDG_RF_SLOTS, rq + b * HDG_RM_Q_SLOTS, nc, max_sweeps,
+                        max_rounds);
 }
 
 // grid (rungs, B): the rungs of a commit are dispatched together and share its matrix in L2;
@@ -420,22 +607,117 @@ __global__ __launch_bounds__(RF_NT) void k_rl_sweep(const int32_t* __restrict__ 
                                                     const int max_sweeps) {
   const size_t b = blockIdx.y, o = (size_t)blockIdx.x * gridDim.y + b;
   const size_t n1 = (size_t)nc - 1;
-  rf_sweep<true>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
-                 merges ? merges + b * n1 * 2 : nullptr, merges ? levels + b * n1 : nullptr,
-                 bounds.tp[blockIdx.x], groups ? groups + o * nc : nullptr,
-                 ut + o * HDG_RF_SLOTS, rq + o * HDG_RF_Q_SLOTS, nc, max_sweeps);
+  rf_sweep<true, false>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
+                        merges ? merges + b * n1 * 2 : nullptr,
+                        merges ? levels + b * n1 : nullptr, bounds.tp[blockIdx.x],
+                        groups ? groups + o * nc : nullptr, ut + o * HDG_RF_SLOTS,
+                        rq + o * HDG_RF_Q_SLOTS, nc, max_sweeps, 1);
 }
 
-// what hdg_refine and hdg_refine_ladder check first, in this order
+// hdg_refine_merge_ladder: k_rl_sweep's block with rounds; rq rows of HDG_RM_Q_SLOTS
+__global__ __launch_bounds__(RF_NT) void k_rml_sweep(const int32_t* __restrict__ ws,
+                                                     const uint32_t* __restrict__ ybits,
+                                                     const int32_t* __restrict__ merges,
+                                                     const float* __restrict__ levels,
+                                                     const rl_bounds bounds, int32_t* groups,
+                                                     u64* __restrict__ ut,
+                                                     long long* __restrict__ rq, const int nc,
+                                                     const int max_sweeps, const int max_rounds) {
+  const size_t b = blockIdx.y, o = (size_t)blockIdx.x * gridDim.y + b;
+  const size_t n1 = (size_t)nc - 1;
+  rf_sweep<true, true>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
+                       merges ? merges + b * n1 * 2 : nullptr,
+                       merges ? levels + b * n1 : nullptr, bounds.tp[blockIdx.x],
+                       groups ? groups + o * nc : nullptr, ut + o * HDG_RF_SLOTS,
+                       rq + o * HDG_RM_Q_SLOTS, nc, max_sweeps, max_rounds);
+}
+
+// what the four entry points check first, in this order.  max_rounds: NULL for the calls
+// without rounds
 inline int rf_check_call(const hdg_shape* s, const int32_t rule, const int32_t max_sweeps,
-                         const int32_t flags, const char* who) {
+                         const int32_t* max_rounds, const int32_t flags, const char* who) {
   if (const int rc = ut_check_shape(s, who)) return rc;
   if (const int rc = ut_check_rule(rule, who)) return rc;
   if (max_sweeps < 1 || max_sweeps > HDG_RF_MAX_SWEEPS)
     return fail(HDG_EINVAL, "%s: max_sweeps must be in [1, %d] (got %d)", who, HDG_RF_MAX_SWEEPS,
                 (int)max_sweeps);
+  if (max_rounds && (*max_rounds < 1 || *max_rounds > HDG_RM_MAX_ROUNDS))
+    return fail(HDG_EINVAL, "%s: max_rounds must be in [1, %d] (got %d)", who, HDG_RM_MAX_ROUNDS,
+                (int)*max_rounds);
   if (flags != 0) return fail(HDG_EINVAL, "%s: unknown flag bits 0x%x", who, (unsigned)flags);
   return 0;
+}
+
+// hdg_refine (max_rounds NULL) and hdg_refine_merge under the name `who`: the checks, the
+// weights launch, the sweep launch
+int rf_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const float* probs,
+            const float threshold, const int32_t rule, const int32_t max_sweeps,
+            const int32_t* max_rounds, const int32_t flags, const int32_t* groups_in,
+            int32_t* groups, uint64_t* ut, int64_t* rq, void* workspace, void* stream) {
+  if (const int rc = rf_check_call(s, rule, max_sweeps, max_rounds, flags, who)) return rc;
+  const float tp = ut_link_bound(rule, threshold);
+  if (!std::isfinite(threshold) || !std::isfinite(tp))
+    return fail(HDG_EINVAL, "%s: threshold %g gives no finite link bound", who,
+                (double)threshold);
+  if (!bt || !bt->ybits || !probs || !groups || !ut || !rq || !workspace)
+    return fail(HDG_EINVAL, "%s: NULL pointer (batch, batch->ybits, probs, groups, ut, "
+                            "rq or workspace)", who);
+  if (const int rc = ut_check_workspace(workspace, who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int nc = s->nc;
+  hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
+                     dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule, tp);
+  if (const int rc = ut_launched(who, "weights")) return rc;
+  if (max_rounds)
+    hipLaunchKernelGGL(k_rm_sweep, dim3((unsigned)s->batch), dim3(RF_NT), 0, st,
+                       (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
+                       (long long*)rq, nc, (int)max_sweeps, (int)*max_rounds);
+  else
+    hipLaunchKernelGGL(k_rf_sweep, dim3((unsigned)s->batch), dim3(RF_NT), 0, st,
+                       (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
+                       (long long*)rq, nc, (int)max_sweeps);
+  return ut_launched(who, "sweep");
+}
+
+// hdg_refine_ladder (max_rounds NULL) and hdg_refine_merge_ladder under the name `who`
+int rl_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const float* probs,
+            const float* thresholds, const int32_t n_rungs, const int32_t rule,
+            const int32_t max_sweeps, const int32_t* max_rounds, const int32_t flags,
+            const int32_t* merges, const float* levels, int32_t* groups, uint64_t* ut,
+            int64_t* rq, void* workspace, void* stream) {
+  if (const int rc = rf_check_call(s, rule, max_sweeps, max_rounds, flags, who)) return rc;
+  if (n_rungs < 1 || n_rungs > HDG_RL_MAX_RUNGS)
+    return fail(HDG_EINVAL, "%s: n_rungs must be in [1, %d] (got %d)", who, HDG_RL_MAX_RUNGS,
+                (int)n_rungs);
+  if (!thresholds) return fail(HDG_EINVAL, "%s: NULL pointer (thresholds)", who);
+  rl_bounds bounds = {};
+  for (int k = 0; k < n_rungs; ++k) {      // each rung's t' once, here, as hdg_refine forms it
+    bounds.tp[k] = ut_link_bound(rule, thresholds[k]);
+    if (!std::isfinite(thresholds[k]) || !std::isfinite(bounds.tp[k]))
+      return fail(HDG_EINVAL, "%s: rung %d: threshold %g gives no finite link bound", who, k,
+                  (double)thresholds[k]);
+  }
+  if ((merges == nullptr) != (levels == nullptr))
+    return fail(HDG_EINVAL, "%s: merges and levels come together or not at all", who);
+  if (!bt || !bt->ybits || !probs || !ut || !rq || !workspace)
+    return fail(HDG_EINVAL, "%s: NULL pointer (batch, batch->ybits, probs, ut, rq or workspace)",
+                who);
+  if (const int rc = ut_check_workspace(workspace, who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int nc = s->nc;
+  hipLaunchKernelGGL(k_rl_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
+                     dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule);
+  if (const int rc = ut_launched(who, "weights")) return rc;
+  const dim3 grid((unsigned)n_rungs, (unsigned)s->batch);
+  if (max_rounds)
+    hipLaunchKernelGGL(k_rml_sweep, grid, dim3(RF_NT), 0, st, (const int32_t*)workspace,
+                       bt->ybits, merges, levels, bounds, groups, (u64*)ut, (long long*)rq, nc,
+                       (int)max_sweeps, (int)*max_rounds);
+  else
+    hipLaunchKernelGGL(k_rl_sweep, grid, dim3(RF_NT), 0, st, (const int32_t*)workspace,
+                       bt->ybits, merges, levels, bounds, groups, (u64*)ut, (long long*)rq, nc,
+                       (int)max_sweeps);
+  return ut_launched(who, "sweep");
 }
 
 }  // namespace
@@ -450,24 +732,17 @@ extern "C" int hdg_refine(const hdg_shape* s, const hdg_batch* bt, const float* 
                           float threshold, int32_t rule, int32_t max_sweeps, int32_t flags,
                           const int32_t* groups_in, int32_t* groups, uint64_t* ut, int64_t* rq,
                           void* workspace, void* stream) {
-  if (const int rc = rf_check_call(s, rule, max_sweeps, flags, "hdg_refine")) return rc;
-  const float tp = ut_link_bound(rule, threshold);
-  if (!std::isfinite(threshold) || !std::isfinite(tp))
-    return fail(HDG_EINVAL, "hdg_refine: threshold %g gives no finite link bound",
-                (double)threshold);
-  if (!bt || !bt->ybits || !probs || !groups || !ut || !rq || !workspace)
-    return fail(HDG_EINVAL, "hdg_refine: NULL pointer (batch, batch->ybits, probs, groups, ut, "
-                            "rq or workspace)");
-  if (const int rc = ut_check_workspace(workspace, "hdg_refine")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int nc = s->nc;
-  hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
-                     dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule, tp);
-  if (const int rc = ut_launched("hdg_refine", "weights")) return rc;
-  hipLaunchKernelGGL(k_rf_sweep, dim3((unsigned)s->batch), dim3(RF_NT), 0, st,
-                     (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
-                     (long long*)rq, nc, (int)max_sweeps);
-  return ut_launched("hdg_refine", "sweep");
+  return rf_call("hdg_refine", s, bt, probs, threshold, rule, max_sweeps, nullptr, flags,
+                 groups_in, groups, ut, rq, workspace, stream);
+}
+
+extern "C" int hdg_refine_merge(const hdg_shape* s, const hdg_batch* bt, const float* probs,
+                                float threshold, int32_t rule, int32_t max_sweeps,
+                                int32_t max_rounds, int32_t flags, const int32_t* groups_in,
+                                int32_t* groups, uint64_t* ut, int64_t* rq, void* workspace,
+                                void* stream) {
+  return rf_call("hdg_refine_merge", s, bt, probs, threshold, rule, max_sweeps, &max_rounds,
+                 flags, groups_in, groups, ut, rq, workspace, stream);
 }
 
 extern "C" size_t hdg_refine_ladder_workspace_bytes(const hdg_shape* s, int32_t flags) {
@@ -481,31 +756,16 @@ extern "C" int hdg_refine_ladder(const hdg_shape* s, const hdg_batch* bt, const 
                                  int32_t max_sweeps, int32_t flags, const int32_t* merges,
                                  const float* levels, int32_t* groups, uint64_t* ut, int64_t* rq,
                                  void* workspace, void* stream) {
-  if (const int rc = rf_check_call(s, rule, max_sweeps, flags, "hdg_refine_ladder")) return rc;
-  if (n_rungs < 1 || n_rungs > HDG_RL_MAX_RUNGS)
-    return fail(HDG_EINVAL, "hdg_refine_ladder: n_rungs must be in [1, %d] (got %d)",
-                HDG_RL_MAX_RUNGS, (int)n_rungs);
-  if (!thresholds) return fail(HDG_EINVAL, "hdg_refine_ladder: NULL pointer (thresholds)");
-  rl_bounds bounds = {};
-  for (int k = 0; k < n_rungs; ++k) {      // each rung's t' once, here, as hdg_refine forms it
-    bounds.tp[k] = ut_link_bound(rule, thresholds[k]);
-    if (!std::isfinite(thresholds[k]) || !std::isfinite(bounds.tp[k]))
-      return fail(HDG_EINVAL, "hdg_refine_ladder: rung %d: threshold %g gives no finite link "
-                              "bound", k, (double)thresholds[k]);
-  }
-  if ((merges == nullptr) != (levels == nullptr))
-    return fail(HDG_EINVAL, "hdg_refine_ladder: merges and levels come together or not at all");
-  if (!bt || !bt->ybits || !probs || !ut || !rq || !workspace)
-    return fail(HDG_EINVAL, "hdg_refine_ladder: NULL pointer (batch, batch->ybits, probs, ut, rq "
-                            "or workspace)");
-  if (const int rc = ut_check_workspace(workspace, "hdg_refine_ladder")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int nc = s->nc;
-  hipLaunchKernelGGL(k_rl_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
-                     dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule);
-  if (const int rc = ut_launched("hdg_refine_ladder", "weights")) return rc;
-  hipLaunchKernelGGL(k_rl_sweep, dim3((unsigned)n_rungs, (unsigned)s->batch), dim3(RF_NT), 0, st,
-                     (const int32_t*)workspace, bt->ybits, merges, levels, bounds, groups,
-                     (u64*)ut, (long long*)rq, nc, (int)max_sweeps);
-  return ut_launched("hdg_refine_ladder", "sweep");
+  return rl_call("hdg_refine_ladder", s, bt, probs, thresholds, n_rungs, rule, max_sweeps,
+                 nullptr, flags, merges, levels, groups, ut, rq, workspace, stream);
+}
+
+extern "C" int hdg_refine_merge_ladder(const hdg_shape* s, const hdg_batch* bt,
+                                       const float* probs, const float* thresholds,
+                                       int32_t n_rungs, int32_t rule, int32_t max_sweeps,
+                                       int32_t max_rounds, int32_t flags, const int32_t* merges,
+                                       const float* levels, int32_t* groups, uint64_t* ut,
+                                       int64_t* rq, void* workspace, void* stream) {
+  return rl_call("hdg_refine_merge_ladder", s, bt, probs, thresholds, n_rungs, rule, max_sweeps,
+                 &max_rounds, flags, merges, levels, groups, ut, rq, workspace, stream);
 }

@@ -86,6 +86,10 @@ RF_Q_START, RF_Q_END, RF_Q_SWEEPS, RF_Q_CONVERGED = range(4)
 RF_MAX_SWEEPS = 64
 # hdg_refine_ladder: the most rungs one call takes (include/hdgnn.h)
 RL_MAX_RUNGS = 64
+# hdg_refine_merge / hdg_refine_merge_ladder: rq rows of RM_Q_SLOTS i64, slots 0 .. 3 as RF_Q_*
+RM_Q_SLOTS = 8
+RM_Q_ROUNDS, RM_Q_MERGES, RM_Q_NODE = 4, 5, 6
+RM_MAX_ROUNDS = 16
 
 
 def untangle_blocks(nc):
@@ -114,7 +118,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_linkage_workspace_bytes", "hdg_linkage",
            "hdg_agglomerate_workspace_bytes", "hdg_agglomerate", "hdg_cut",
            "hdg_refine_workspace_bytes", "hdg_refine",
-           "hdg_refine_ladder_workspace_bytes", "hdg_refine_ladder"]
+           "hdg_refine_ladder_workspace_bytes", "hdg_refine_ladder",
+           "hdg_refine_merge", "hdg_refine_merge_ladder"]
 
 _lib = None
 
@@ -172,6 +177,10 @@ def load(path=None):
     lib.hdg_refine_ladder_workspace_bytes.restype = ctypes.c_size_t
     lib.hdg_refine_ladder.argtypes = [P(Shape), P(Batch), vp, P(f32), i32, i32, i32, i32, vp, vp,
                                       vp, vp, vp, vp, vp]
+    lib.hdg_refine_merge.argtypes = [P(Shape), P(Batch), vp, f32, i32, i32, i32, i32, vp, vp, vp,
+                                     vp, vp, vp]
+    lib.hdg_refine_merge_ladder.argtypes = [P(Shape), P(Batch), vp, P(f32), i32, i32, i32, i32,
+                                            i32, vp, vp, vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

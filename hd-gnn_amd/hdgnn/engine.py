@@ -541,6 +541,24 @@ class Engine:
         start and the end, the sweeps run and whether the last one made no move.  `probs` as
         untangle()'s.  Enqueued on the current stream; nothing is copied to the host.  The
         workspace is allocated on the first call and kept."""
+        return self._refine(dbatch, groups, probs, threshold, rule, max_sweeps, None)
+
+    def refine_merge(self, dbatch, groups=None, probs=None, threshold=0.5, rule="mean",
+                     max_sweeps=8, max_rounds=4):
+        """hdg_refine_merge: refine() in at most `max_rounds` rounds (1 to RM_MAX_ROUNDS), a
+        round being refine()'s node sweeps followed by one group sweep in which whole groups
+        merge (include/hdgnn.h); `max_sweeps` is the total of node sweeps -> (groups int32
+        [B][nc], ut int64 [B][RF_SLOTS], rq int64 [B][RM_Q_SLOTS]) as fresh device tensors: as
+        refine()'s, RF_MOVES counting node moves only and rq holding four more slots (the
+        rounds run, the merges made, the objective after the first node phase, 0).  Arguments,
+        stream and workspace as refine()'s."""
+        if not (isinstance(max_rounds, int) and 1 <= max_rounds <= _lib.RM_MAX_ROUNDS):
+            raise ValueError("max_rounds must be an int in [1, %d] (got %r)"
+                             % (_lib.RM_MAX_ROUNDS, max_rounds))
+        return self._refine(dbatch, groups, probs, threshold, rule, max_sweeps, max_rounds)
+
+    def _refine(self, dbatch, groups, probs, threshold, rule, max_sweeps, max_rounds):
+        """refine() (max_rounds None) and refine_merge(): the checks, the outputs, the call."""
         self._check(dbatch)
         probs = self._decode_probs(probs)
         rule = self._rule(rule)
@@ -557,18 +575,18 @@ class Engine:
         out = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
         # u64 counts, every value < 2^63: int64 reads them as they are
         ut = torch.empty(self.batch, _lib.RF_SLOTS, dtype=torch.int64, device=self.device)
-        rq = torch.empty(self.batch, _lib.RF_Q_SLOTS, dtype=torch.int64, device=self.device)
+        rq = torch.empty(self.batch, _lib.RF_Q_SLOTS if max_rounds is None else _lib.RM_Q_SLOTS,
+                         dtype=torch.int64, device=self.device)
         b = dbatch.struct()
-        _lib.check(self.lib.hdg_refine(ctypes.byref(self.shape), ctypes.byref(b),
-                                       ctypes.c_void_p(probs.data_ptr()),
-                                       ctypes.c_float(threshold), rule, max_sweeps, 0,
-                                       None if groups is None
-                                       else ctypes.c_void_p(groups.data_ptr()),
-                                       ctypes.c_void_p(out.data_ptr()),
-                                       ctypes.c_void_p(ut.data_ptr()),
-                                       ctypes.c_void_p(rq.data_ptr()),
-                                       ctypes.c_void_p(ws.data_ptr()),
-                                       self._stream()))
+        call, budget = ((self.lib.hdg_refine, (max_sweeps,)) if max_rounds is None
+                        else (self.lib.hdg_refine_merge, (max_sweeps, max_rounds)))
+        _lib.check(call(ctypes.byref(self.shape), ctypes.byref(b),
+                        ctypes.c_void_p(probs.data_ptr()), ctypes.c_float(threshold), rule,
+                        *budget, 0,
+                        None if groups is None else ctypes.c_void_p(groups.data_ptr()),
+                        ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ut.data_ptr()),
+                        ctypes.c_void_p(rq.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                        self._stream()))
         return out, ut, rq
 
     def refine_ladder(self, dbatch, thresholds, tree=None, probs=None, rule="mean", max_sweeps=8,
@@ -582,6 +600,23 @@ class Engine:
         (hdgnn.metrics.best_rung picks the rung).  `probs` as untangle()'s.  Enqueued on the
         current stream; nothing is copied to the host; a captured graph replays the captured
         thresholds.  The workspace is allocated on the first call and kept."""
+        return self._refine_ladder(dbatch, thresholds, tree, probs, rule, max_sweeps, None, groups)
+
+    def refine_merge_ladder(self, dbatch, thresholds, tree=None, probs=None, rule="mean",
+                            max_sweeps=8, max_rounds=4, groups=False):
+        """hdg_refine_merge_ladder: refine_ladder() with refine_merge()'s rounds at every rung
+        -> (ut int64 [T][B][RF_SLOTS], rq int64 [T][B][RM_Q_SLOTS], groups int32 [T][B][nc] or
+        None unless `groups`): rung k holds what cut() then refine_merge() at thresholds[k]
+        return.  Arguments, stream and workspace as refine_ladder()'s."""
+        if not (isinstance(max_rounds, int) and 1 <= max_rounds <= _lib.RM_MAX_ROUNDS):
+            raise ValueError("max_rounds must be an int in [1, %d] (got %r)"
+                             % (_lib.RM_MAX_ROUNDS, max_rounds))
+        return self._refine_ladder(dbatch, thresholds, tree, probs, rule, max_sweeps, max_rounds,
+                                   groups)
+
+    def _refine_ladder(self, dbatch, thresholds, tree, probs, rule, max_sweeps, max_rounds, groups):
+        """refine_ladder() (max_rounds None) and refine_merge_ladder(): the checks, the
+        outputs, the call."""
         self._check(dbatch)
         probs = self._decode_probs(probs)
         rule = self._rule(rule)
@@ -615,11 +650,14 @@ class Engine:
                if groups else None)
         # u64 counts, every value < 2^63: int64 reads them as they are
         ut = torch.empty(T, self.batch, _lib.RF_SLOTS, dtype=torch.int64, device=self.device)
-        rq = torch.empty(T, self.batch, _lib.RF_Q_SLOTS, dtype=torch.int64, device=self.device)
+        rq = torch.empty(T, self.batch, _lib.RF_Q_SLOTS if max_rounds is None else _lib.RM_Q_SLOTS,
+                         dtype=torch.int64, device=self.device)
         b = dbatch.struct()
-        _lib.check(self.lib.hdg_refine_ladder(
+        call, budget = ((self.lib.hdg_refine_ladder, (max_sweeps,)) if max_rounds is None
+                        else (self.lib.hdg_refine_merge_ladder, (max_sweeps, max_rounds)))
+        _lib.check(call(
             ctypes.byref(self.shape), ctypes.byref(b), ctypes.c_void_p(probs.data_ptr()),
-            (ctypes.c_float * T)(*thr), T, rule, max_sweeps, 0,
+            (ctypes.c_float * T)(*thr), T, rule, *budget, 0,
             None if merges is None else ctypes.c_void_p(merges.data_ptr()),
             None if levels is None else ctypes.c_void_p(levels.data_ptr()),
             None if out is None else ctypes.c_void_p(out.data_ptr()),

@@ -616,6 +616,74 @@ def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8
     Plain: per visit of p one np.bincount of row p of the gains over the slots, then the
     choice among stay, the other non-empty slots and the smallest empty slot (strictly above
     stay; the largest; a non-empty slot before the empty one, then the lowest slot)."""
+    return _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, None)
+
+
+def _node_phase(A, slot, size, budget):
+    """hdg_refine's sweeps on one commit's gains A, in place on slot and size: until a sweep
+    makes no move or `budget` sweeps have run -> (moves, sweeps, converged, gain in Q)."""
+    nc = len(slot)
+    moves = sweeps = conv = gain = 0
+    while sweeps < budget and not conv:
+        moved = 0
+        for p in range(nc):
+            s = np.bincount(slot, weights=A[p], minlength=nc).astype(np.int64)   # exact
+            g = int(slot[p])
+            stay, best, to = int(s[g]), None, -1
+            cand = size > 0
+            cand[g] = False
+            if cand.any():
+                m = int(s[cand].max())
+                if m > stay:
+                    best, to = m, int(np.flatnonzero(cand & (s == m))[0])
+            if size[g] > 1 and 0 > stay and (best is None or 0 > best):
+                best, to = 0, int(np.flatnonzero(size == 0)[0])
+            if best is not None:
+                slot[p] = to
+                size[g] -= 1
+                size[to] += 1
+                gain += best - stay
+                moved += 1
+        sweeps += 1
+        moves += moved
+        conv = int(moved == 0)
+    return moves, sweeps, conv, gain
+
+
+def _group_sweep(A, slot, size):
+    """One group sweep of hdg_refine_merge (include/hdgnn.h) on one commit's gains A, in place
+    on slot and size -> (merges, gain in Q).  Per visit of a non-empty slot g: C[h] = the sum
+    of the gains between g's members and slot h's, one exact integer sum per slot; the largest
+    C[h] over the other non-empty slots, strictly above 0, the lowest h among equals; the
+    members of max(g, h) move into min(g, h)."""
+    nc = len(slot)
+    merges = gain = 0
+    for g in range(nc):
+        if size[g] == 0:
+            continue
+        c = A[slot == g].sum(0)                            # int64: per hunk q, over g's members
+        C = np.zeros(nc, np.int64)
+        np.add.at(C, slot, c)
+        cand = size > 0
+        cand[g] = False
+        if not cand.any():
+            continue
+        m = int(C[cand].max())
+        if m <= 0:
+            continue
+        h = int(np.flatnonzero(cand & (C == m))[0])
+        to, frm = min(g, h), max(g, h)
+        slot[slot == frm] = to
+        size[to] += size[frm]
+        size[frm] = 0
+        gain += m
+        merges += 1
+    return merges, gain
+
+
+def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds):
+    """refine (max_rounds None) and refine_merge: the checks, the start, the node phase --
+    alone, or in rounds with a group sweep after each -- and the rows."""
     from .data import pair_index
     if rule not in UT_RULES:
         raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
@@ -626,6 +694,8 @@ def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8
         raise ValueError("threshold %r gives no finite link bound" % (threshold,))
     if not 1 <= int(max_sweeps) <= RF_MAX_SWEEPS:
         raise ValueError("max_sweeps must be in [1, %d] (got %r)" % (RF_MAX_SWEEPS, max_sweeps))
+    if max_rounds is not None and not 1 <= int(max_rounds) <= RM_MAX_ROUNDS:
+        raise ValueError("max_rounds must be in [1, %d] (got %r)" % (RM_MAX_ROUNDS, max_rounds))
     label = np.asarray(label_onehot)
     probs = np.asarray(probs, np.float32)
     B, R = probs.shape[0], probs.shape[2]
@@ -636,7 +706,7 @@ def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8
     iu, ju = np.triu_indices(nc, 1)
     ut = np.zeros((B, RF_SLOTS), np.int64)
     out = np.zeros((B, nc), np.int32)
-    rq = np.zeros((B, RF_Q_SLOTS), np.int64)
+    rq = np.zeros((B, RF_Q_SLOTS if max_rounds is None else RM_Q_SLOTS), np.int64)
     Y = np.zeros((nc, nc), bool)
     every = np.arange(nc)
     for b in range(B):
@@ -649,31 +719,20 @@ def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8
             slot[ok] = low[groups[b][ok]]
         size = np.bincount(slot, minlength=nc)
         q0 = int(A[iu, ju][slot[iu] == slot[ju]].sum())
-        moves = sweeps = conv = 0
-        q1 = q0
-        while sweeps < int(max_sweeps) and not conv:
-            moved = 0
-            for p in range(nc):
-                s = np.bincount(slot, weights=A[p], minlength=nc).astype(np.int64)   # exact
-                g = int(slot[p])
-                stay, best, to = int(s[g]), None, -1
-                cand = size > 0
-                cand[g] = False
-                if cand.any():
-                    m = int(s[cand].max())
-                    if m > stay:
-                        best, to = m, int(np.flatnonzero(cand & (s == m))[0])
-                if size[g] > 1 and 0 > stay and (best is None or 0 > best):
-                    best, to = 0, int(np.flatnonzero(size == 0)[0])
-                if best is not None:
-                    slot[p] = to
-                    size[g] -= 1
-                    size[to] += 1
-                    q1 += best - stay
-                    moved += 1
-            sweeps += 1
-            moves += moved
-            conv = int(moved == 0)
+        moves, sweeps, conv, gain = _node_phase(A, slot, size, int(max_sweeps))
+        q1 = q0 + gain
+        if max_rounds is not None:
+            rounds, merges, qn = 0, 0, q1
+            while True:
+                merged, gain = _group_sweep(A, slot, size)
+                rounds += 1
+                merges += merged
+                q1 += gain
+                conv = int(conv and not merged)
+                if not merged or rounds >= int(max_rounds) or sweeps >= int(max_sweeps):
+                    break
+                m, s, conv, gain = _node_phase(A, slot, size, int(max_sweeps) - sweeps)
+                moves, sweeps, q1 = moves + m, sweeps + s, q1 + gain
         low = np.full(nc, nc, np.int64)
         np.minimum.at(low, slot, every)
         lab = low[slot]                            # every hunk's smallest group member
@@ -686,8 +745,34 @@ def refine(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8
         ut[b] = (int(g.max()) + 1, int(t.max()) + 1, np.count_nonzero(sp & st),
                  np.count_nonzero(sp & ~st), np.count_nonzero(~sp & st),
                  np.count_nonzero(~sp & ~st), moves, nans)
-        rq[b] = (q0, q1, sweeps, conv)
+        rq[b, :RF_Q_SLOTS] = (q0, q1, sweeps, conv)
+        if max_rounds is not None:
+            rq[b, RF_Q_SLOTS:] = (rounds, merges, qn, 0)
     return ut, out, rq
+
+
+# ---------------------------------------------------------------------------------------
+# Refinement with rounds: after every node phase one group sweep, in which whole groups merge,
+# as hdg_refine_merge and hdg_refine_merge_ladder run them on the device (include/hdgnn.h,
+# HDG_RM_*), their host restatements.
+# ---------------------------------------------------------------------------------------
+RM_Q_SLOTS = 8
+RM_Q_ROUNDS, RM_Q_MERGES, RM_Q_NODE = 4, 5, 6
+RM_MAX_ROUNDS = 16
+
+
+def refine_merge(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8,
+                 max_rounds=4):
+    """refine() with rounds -> (ut int64 (B, RF_SLOTS), groups int32 (B, Nc), rq int64
+    (B, RM_Q_SLOTS)): the host restatement of hdg_refine_merge, definitions as in
+    include/hdgnn.h.  A round is refine's node phase, then one group sweep (per visit of a
+    non-empty slot one exact sum per slot of the gains between the two slots' members, and
+    the best merge strictly above 0); until a group sweep merges nothing, `max_rounds` rounds
+    have run or the node sweeps of all rounds reach `max_sweeps`.  RF_MOVES counts node moves
+    only; rq adds the rounds, the merges and Q after the first node phase."""
+    if max_rounds is None:
+        raise ValueError("max_rounds must be in [1, %d] (got None)" % RM_MAX_ROUNDS)
+    return _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds)
 
 
 # ---------------------------------------------------------------------------------------
@@ -735,6 +820,25 @@ def refine_ladder(label_onehot, probs, thresholds, tree=None, rule="mean", max_s
             with np.errstate(over="ignore"):
                 start = cut_groups(tree[0], tree[1], t + t if rule == "mean" else t)
         out.append(refine(label_onehot, probs, start, t, rule, max_sweeps))
+    return tuple(np.stack([o[i] for o in out]) for i in range(3))
+
+
+def refine_merge_ladder(label_onehot, probs, thresholds, tree=None, rule="mean", max_sweeps=8,
+                        max_rounds=4):
+    """refine_ladder() with rounds -> (ut int64 (T, B, RF_SLOTS), groups int32 (T, B, Nc), rq
+    int64 (T, B, RM_Q_SLOTS)): the host restatement of hdg_refine_merge_ladder.  A loop: per
+    rung cut_groups at the rung's link bound (None: every hunk alone), then refine_merge at
+    the rung."""
+    thr = _rungs(thresholds)
+    if rule not in UT_RULES:
+        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
+    out = []
+    for t in thr:
+        start = None
+        if tree is not None:
+            with np.errstate(over="ignore"):
+                start = cut_groups(tree[0], tree[1], t + t if rule == "mean" else t)
+        out.append(refine_merge(label_onehot, probs, start, t, rule, max_sweeps, max_rounds))
     return tuple(np.stack([o[i] for o in out]) for i in range(3))
 
 

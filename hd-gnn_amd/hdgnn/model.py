@@ -598,8 +598,18 @@ class graph2graph(object):
             print('eval nan relations: %d' % scores["nan_relations"])
         return scores, table
 
+    @staticmethod
+    def _check_merge(merge, refine):
+        """untangle()'s and calibrate_refined()'s `merge`: the rounds of hdg_refine_merge."""
+        if not (isinstance(merge, int) and 0 <= merge <= _lib.RM_MAX_ROUNDS):
+            raise ValueError("merge must be an int in [0, %d] (got %r)"
+                             % (_lib.RM_MAX_ROUNDS, merge))
+        if merge and refine < 1:
+            raise ValueError("merge > 0 needs refine >= 1 (got refine = %r)" % (refine,))
+
     # ------------------------------------------------------------------ untangle
-    def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single", refine=0):
+    def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single", refine=0,
+                 merge=0):
         """Untangle the commits of the test (or train) split with the trained classifier: per
         batch Engine.forward then Engine.untangle (hdg_untangle), so only each commit's hunk
         group ids and its integer row (include/hdgnn.h, HDG_UT_*) come to the host, never the
@@ -615,7 +625,11 @@ class graph2graph(object):
         refine > 0: the groups of either path go through Engine.refine (hdg_refine: at most
         `refine` best-move sweeps at the same threshold and rule); the refined groups and
         table (slot 6: the moves made) are what is returned and saved, and
-        untangle_refine<Ne>.npy holds each commit's objective row (HDG_RF_Q_*)."""
+        untangle_refine<Ne>.npy holds each commit's objective row (HDG_RF_Q_*).
+        merge > 0 (needs refine >= 1): the refinement is Engine.refine_merge (hdg_refine_merge:
+        at most `merge` rounds of node sweeps and one group sweep, `refine` the total of node
+        sweeps); the objective rows have 8 columns, the first four with their meaning
+        (HDG_RM_Q_*), and one more line reports rounds, merges and the objective."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
@@ -625,6 +639,8 @@ class graph2graph(object):
         if not (isinstance(refine, int) and 0 <= refine <= _lib.RF_MAX_SWEEPS):
             raise ValueError("refine must be an int in [0, %d] (got %r)"
                              % (_lib.RF_MAX_SWEEPS, refine))
+        self._check_merge(merge, refine)
+        qslots = _lib.RM_Q_SLOTS if merge else _lib.RF_Q_SLOTS
         _, _, train, test, maps = self._compact()
         if self.load(self.checkpoint_dir):
             print(" [*] Load SUCCESS")
@@ -639,7 +655,11 @@ class graph2graph(object):
             else:
                 m, lv, cv, _, lk = eng.agglomerate(db, rule=rule, method=method)
                 g, ut = eng.cut(m, lv, cv, lk, threshold=threshold, rule=rule)
-            if refine:
+            if merge:
+                g, ut, rq = eng.refine_merge(db, g, threshold=threshold, rule=rule,
+                                             max_sweeps=refine, max_rounds=merge)
+                qs.append(rq)
+            elif refine:
                 g, ut, rq = eng.refine(db, g, threshold=threshold, rule=rule, max_sweeps=refine)
                 qs.append(rq)
             ids.append(g)
@@ -656,11 +676,11 @@ class graph2graph(object):
             groups = groups.transpose(1, 0, 2, 3)
         if refine:
             qrows = (torch.stack(qs).cpu().numpy() if nb
-                     else np.zeros((0, lb, _lib.RF_Q_SLOTS), np.int64))
+                     else np.zeros((0, lb, qslots), np.int64))
             if self.world > 1 and nb:
-                qrows = self._gather(qrows).reshape(self.world, nb, lb, _lib.RF_Q_SLOTS)
+                qrows = self._gather(qrows).reshape(self.world, nb, lb, qslots)
                 qrows = qrows.transpose(1, 0, 2, 3)
-            qrows = np.ascontiguousarray(qrows.reshape(-1, _lib.RF_Q_SLOTS)).astype(np.int64)
+            qrows = np.ascontiguousarray(qrows.reshape(-1, qslots)).astype(np.int64)
         table = np.ascontiguousarray(table.reshape(-1, _lib.UT_SLOTS)).astype(np.int64)
         groups = np.ascontiguousarray(groups.reshape(-1, self.Nc)).astype(np.int32)
         scores = metrics.scores_from_untangle(table)
@@ -679,6 +699,12 @@ class graph2graph(object):
                          int(qrows[:, _lib.RF_Q_CONVERGED].sum()), len(qrows)))
                 print('untangle refine objective: %d -> %d'
                       % (int(qrows[:, _lib.RF_Q_START].sum()), int(qrows[:, _lib.RF_Q_END].sum())))
+            if merge:
+                print('untangle merge: %d rounds at most, %d rounds, %d merges, objective after '
+                      'the first node phase %d -> %d at the end'
+                      % (merge, int(qrows[:, _lib.RM_Q_ROUNDS].sum()),
+                         int(qrows[:, _lib.RM_Q_MERGES].sum()),
+                         int(qrows[:, _lib.RM_Q_NODE].sum()), int(qrows[:, _lib.RF_Q_END].sum())))
             for name in ("rand", "precision", "recall", "f1"):
                 print('untangle %s: %s (per-commit mean %s)' % (name, scores[name],
                                                                 scores[name + "_mean"]))
@@ -752,7 +778,7 @@ class graph2graph(object):
 
     # ------------------------------------------------------------------ calibrate_refined
     def calibrate_refined(self, args, part="train", rule="mean", score="f1", method="single",
-                          refine=8, ladder=(0.05, 0.95, 19)):
+                          refine=8, ladder=(0.05, 0.95, 19), merge=0):
         """The link threshold untangle(refine=N) should use: the rung of `ladder` = (lo, hi, n)
         (metrics.ladder) with the best pooled `score` of the REFINED groups over the commits of
         the train (or test) split -- the objective's threshold is not the tree's best cut,
@@ -766,7 +792,11 @@ class graph2graph(object):
         [T][n_commits][4]); rank 0 prints one line per rung, the chosen rung and the tree's
         own best (metrics.best_threshold on the same trees) beside it, and writes
         refine_ladder_thresholds<Ne>.npy, refine_ladder_counts<Ne>.npy and
-        refine_ladder_objective<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/."""
+        refine_ladder_objective<Ne>.npy under outputSelf/<Repo>/model_<v>/<Step>/.
+        merge > 0: the threshold untangle(refine=N, merge=R) should use -- the ladder is
+        Engine.refine_merge_ladder (hdg_refine_merge_ladder), every rung refined in at most
+        `merge` rounds; rq has 8 columns, the first four with their meaning, and each rung's
+        line is followed by one with its rounds, merges and objective."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
@@ -776,6 +806,8 @@ class graph2graph(object):
         if not (isinstance(refine, int) and 1 <= refine <= _lib.RF_MAX_SWEEPS):
             raise ValueError("refine must be an int in [1, %d] (got %r)"
                              % (_lib.RF_MAX_SWEEPS, refine))
+        self._check_merge(merge, refine)
+        qslots = _lib.RM_Q_SLOTS if merge else _lib.RF_Q_SLOTS
         thresholds = metrics.ladder(*ladder)
         T = len(thresholds)
         _, _, train, test, maps = self._compact()
@@ -789,13 +821,18 @@ class graph2graph(object):
             eng.forward(db)
             m, lv, cv, _, lk = (eng.linkage(db, rule=rule) if method == "single"
                                 else eng.agglomerate(db, rule=rule, method=method))
-            ut, rq, _ = eng.refine_ladder(db, thresholds.tolist(), tree=(m, lv), rule=rule,
-                                          max_sweeps=refine)
+            if merge:
+                ut, rq, _ = eng.refine_merge_ladder(db, thresholds.tolist(), tree=(m, lv),
+                                                    rule=rule, max_sweeps=refine,
+                                                    max_rounds=merge)
+            else:
+                ut, rq, _ = eng.refine_ladder(db, thresholds.tolist(), tree=(m, lv), rule=rule,
+                                              max_sweeps=refine)
             # batch-major like the tree's arrays, the rungs inside: [lb][T][slots]
             outs.append((lv, cv, lk, ut.transpose(0, 1).contiguous(),
                          rq.transpose(0, 1).contiguous()))
         nb, lb, n1 = len(outs), self.local_batch, self.Nc - 1
-        tails = ((n1,), (n1, 2), (_lib.LK_SLOTS,), (T, _lib.RF_SLOTS), (T, _lib.RF_Q_SLOTS))
+        tails = ((n1,), (n1, 2), (_lib.LK_SLOTS,), (T, _lib.RF_SLOTS), (T, qslots))
         dtypes = (np.float32, np.int32, np.int64, np.int64, np.int64)
         arrs = [(torch.stack([o[i] for o in outs]).cpu().numpy() if nb
                  else np.zeros((0, lb) + tails[i], dtypes[i])) for i in range(5)]
@@ -827,6 +864,13 @@ class graph2graph(object):
                       % (j, float(thresholds[j]), score, vals[j],
                          int(table[j, :, _lib.RF_MOVES].sum()),
                          int(qrows[j, :, _lib.RF_Q_CONVERGED].sum()), n))
+                if merge:
+                    print('calibrate refined rung %d merge: %d rounds, %d merges, objective '
+                          'after the first node phase %d -> %d at the end'
+                          % (j, int(qrows[j, :, _lib.RM_Q_ROUNDS].sum()),
+                             int(qrows[j, :, _lib.RM_Q_MERGES].sum()),
+                             int(qrows[j, :, _lib.RM_Q_NODE].sum()),
+                             int(qrows[j, :, _lib.RF_Q_END].sum())))
             print('calibrate refined threshold: %r (rung %d), %s = %s' % (threshold, k, score, best))
             print('calibrate refined tree alone: threshold %r, %s = %s' % (tree_thr, score,
                                                                           tree_best))

@@ -23,6 +23,9 @@ MI355X instead of a TF1 session.
                                                # groups: the best rung of the ladder LO:HI:N
     python hd-gnn_amd/main.py --Type calibrate --link-threshold refined --link-refine 8
                                                # that threshold alone (one ladder call per batch)
+    python hd-gnn_amd/main.py --Type untangle --link-threshold refined --link-refine 8 \\
+        --link-merge 4                         # ... whole groups may merge between the sweeps:
+                                               # up to 4 rounds of node sweeps + one group sweep
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -80,7 +83,11 @@ def _variant(argv):
     REFINED with at most --link-refine N sweeps (N >= 1 is required), among the rungs of
     --link-ladder LO:HI:N (default 0.05:0.95:19), every rung cut from the commits' merge trees
     and refined in one call (hdg_refine_ladder); --Type calibrate computes it alone, --Type
-    untangle uses it."""
+    untangle uses it;
+    --link-merge R (default 0: none; at most 16; needs --link-refine N >= 1): the refinement
+    runs in at most R rounds, each the node sweeps followed by one group sweep in which whole
+    groups merge, N the total of node sweeps (hdg_refine_merge, hdg_refine_merge_ladder), in
+    --Type untangle and in the ladder of --link-threshold refined alike."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
@@ -90,9 +97,14 @@ def _variant(argv):
     p.add_argument('--link-method', default='single', choices=('single', 'complete', 'average'))
     p.add_argument('--link-refine', type=int, default=0)
     p.add_argument('--link-ladder', type=_ladder, default=(0.05, 0.95, 19))
+    p.add_argument('--link-merge', type=int, default=0)
     a, rest = p.parse_known_args(argv)
     if a.link_threshold == 'refined' and a.link_refine < 1:
         p.error("--link-threshold refined needs --link-refine N with N >= 1")
+    if not 0 <= a.link_merge <= 16:
+        p.error("--link-merge R needs 0 <= R <= 16")
+    if a.link_merge and a.link_refine < 1:
+        p.error("--link-merge needs --link-refine N with N >= 1")
     return a, rest
 
 
@@ -168,6 +180,9 @@ def main(argv=None, model_cls=None):
         # the threshold calibrated for the refined groups: the best rung of the ladder
         refined = dict(rule=extra.link_rule, score=extra.link_score, refine=extra.link_refine,
                        ladder=extra.link_ladder, **how)
+        # rounds with group sweeps only when asked for: without the flag every call is as it was
+        rounds = {'merge': extra.link_merge} if extra.link_merge else {}
+        refined.update(rounds)
         if args.Type == 'untangle':  # not in the reference: hunk groups per commit, on the device
             threshold = extra.link_threshold
             if threshold == 'refined':
@@ -177,7 +192,8 @@ def main(argv=None, model_cls=None):
                                             score=extra.link_score, **how)[0]
             # without refinement the call is the one it always was
             more = {'refine': extra.link_refine} if extra.link_refine else {}
-            model.untangle(args, threshold=threshold, rule=extra.link_rule, **how, **more)
+            model.untangle(args, threshold=threshold, rule=extra.link_rule, **how, **more,
+                           **rounds)
         if args.Type == 'calibrate':  # not in the reference: the best link threshold, on the device
             if extra.link_threshold == 'refined':
                 model.calibrate_refined(args, part="train", **refined)

@@ -20,7 +20,8 @@
  *   - every pointer is a caller-owned DEVICE pointer (the library never allocates);
  *     `stream` is a hipStream_t passed as void*; all work is enqueued on it, no host
  *     synchronisation happens inside any call (graph-capturable).  The one exception:
- *     hdg_refine_ladder's `thresholds` is a HOST array, read during the call only.
+ *     hdg_refine_ladder's and hdg_refine_merge_ladder's `thresholds` is a HOST array, read
+ *     during the call only.
  *   - return 0 on success, HDG_EINVAL for a shape/argument error, or the hipError_t
  *     of a failed launch; hdg_last_error() gives a thread-local message.
  *   - parameters are one flat fp32 vector in tf.global_variables() order with TF
@@ -609,6 +610,86 @@ int    hdg_refine_ladder(const hdg_shape* shape, const hdg_batch* batch, const f
                          uint64_t* ut     /* [n_rungs][batch][HDG_RF_SLOTS] */,
                          int64_t* rq      /* [n_rungs][batch][HDG_RF_Q_SLOTS] */,
                          void* workspace, void* stream);
+
+/* hdg_refine_merge, hdg_refine_merge_ladder: hdg_refine and hdg_refine_ladder with ROUNDS.
+ * hdg_refine's only move is one hunk to another slot, so two groups that belong together but
+ * are each internally tight stay apart: every single hunk loses more by leaving its half than
+ * it gains from the other, no move is accepted and the search reports "converged".  A round
+ * is hdg_refine's node sweeps followed by one GROUP SWEEP, in which whole groups merge
+ * (hdgnn.metrics.refine_merge and refine_merge_ladder restate the calls, integer for integer).
+ * Everything not restated here -- weights, pairs that are no edge, the gain a_pq, the bound t',
+ * the start and the slots, the node sweep and its tie rules, the dense output ids, the ut row
+ * and its HDG_RF_NAN count -- is hdg_refine's, above.
+ *
+ *   group sweep  visits the slots g = 0, 1, .., nc-1 in that order, each visit seeing the merges
+ *            of the earlier visits of the same sweep.  A slot that is empty when its turn
+ *            comes is skipped.  For a non-empty g and every other non-empty slot h,
+ *            C[h] = the sum of a_pq over p in g and q in h (int64; a pair that is no edge adds
+ *            0).  If the largest C[h] is strictly above 0, g merges with that h; among equal
+ *            values the lowest h wins.  The members of slot max(g, h) move into slot
+ *            min(g, h), and Q rises by C[h].  One merge per visit; there is no empty-slot
+ *            candidate
+ *   bounds   |C| <= (nc / 2)^2 * 2^19 <= 2^39, so a 64-bit key holds the value biased by 2^40
+ *            and an 11-bit tie field
+ *   rounds   max_sweeps in [1, HDG_RF_MAX_SWEEPS] is the call's total budget of node sweeps,
+ *            max_rounds is in [1, HDG_RM_MAX_ROUNDS].  Repeat: (1) the node phase, hdg_refine's
+ *            sweeps until a sweep makes no move or the total of sweeps reaches max_sweeps;
+ *            (2) one group sweep; (3) stop if that group sweep merged nothing, or max_rounds
+ *            rounds have run, or the total of sweeps has reached max_sweeps.  Every move and
+ *            every merge raises Q by at least 1
+ *   rq       rows of HDG_RM_Q_SLOTS i64: slots 0 .. 3 as HDG_RF_Q_START / END / SWEEPS /
+ *            CONVERGED, where SWEEPS is the total of node sweeps and CONVERGED is 1 iff the
+ *            last node phase ended on a sweep without a move and the last group sweep merged
+ *            nothing; then HDG_RM_Q_ROUNDS, HDG_RM_Q_MERGES, HDG_RM_Q_NODE (Q after the first
+ *            node phase) and one slot written as 0
+ *   ut       hdg_refine's row of the final partition; HDG_RF_MOVES counts node moves only
+ * Two consequences: (A) the state after the first node phase is exactly hdg_refine's final
+ * state at the same max_sweeps, so HDG_RM_Q_NODE equals hdg_refine's HDG_RF_Q_END, and if the
+ * first group sweep merges nothing then groups, ut and rq[0 .. 3] equal hdg_refine's, with
+ * ROUNDS = 1 and MERGES = 0; (B) Q_END - Q_NODE >= MERGES.
+ * hdg_refine_merge_ladder: rung k of groups ([n_rungs][batch][nc], or NULL), ut
+ * ([n_rungs][batch][HDG_RF_SLOTS]) and rq ([n_rungs][batch][HDG_RM_Q_SLOTS]) holds, integer
+ * for integer, what hdg_cut(merges, levels, thresholds[k], rule) followed by
+ * hdg_refine_merge(thresholds[k], rule, max_sweeps, max_rounds, groups_in = those groups)
+ * writes -- or hdg_refine_merge with groups_in NULL without a tree; thresholds is a HOST array
+ * as hdg_refine_ladder's.
+ * The workspaces are hdg_refine_workspace_bytes and hdg_refine_ladder_workspace_bytes.  Two
+ * launches each: the weights kernel of hdg_refine / hdg_refine_ladder, unchanged, and the
+ * sweep block with rounds (k_rm_sweep, k_rml_sweep).  In a group sweep the members of every
+ * slot are chained in LDS once; a visit sums the rows of g's members per hunk in registers
+ * (int32), then per slot with two int32 LDS atomics on a 16-bit split (exact), picks the block
+ * maximum of the keys, and a merge appends one chain to the other: at most nc row reads per
+ * group sweep and two barriers per non-empty slot.  The round loop is bounded by max_rounds,
+ * the visits by nc, a chain walk by the slot's size, the total of sweeps by max_sweeps.  No
+ * host synchronisation, no block waits for another, no float atomics, no allocation:
+ * graph-capturable, the same bits on every run.  HDG_EINVAL (the message starts
+ * "hdg_refine_merge:" or "hdg_refine_merge_ladder:"; nothing is launched) for everything
+ * hdg_refine or hdg_refine_ladder rejects, max_rounds out of range, or any flag bit.       */
+#define HDG_RM_Q_SLOTS 8
+#define HDG_RM_Q_ROUNDS 4      /* rounds run                                               */
+#define HDG_RM_Q_MERGES 5      /* merges made by the group sweeps                          */
+#define HDG_RM_Q_NODE 6        /* Q after the first node phase                             */
+#define HDG_RM_MAX_ROUNDS 16
+
+int    hdg_refine_merge(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                        float threshold, int32_t rule, int32_t max_sweeps, int32_t max_rounds,
+                        int32_t flags,
+                        const int32_t* groups_in /* [batch][nc] or NULL */,
+                        int32_t* groups          /* [batch][nc] */,
+                        uint64_t* ut             /* [batch][HDG_RF_SLOTS] */,
+                        int64_t* rq              /* [batch][HDG_RM_Q_SLOTS] */,
+                        void* workspace, void* stream);
+int    hdg_refine_merge_ladder(const hdg_shape* shape, const hdg_batch* batch,
+                               const float* probs,
+                               const float* thresholds /* HOST, [n_rungs] */, int32_t n_rungs,
+                               int32_t rule, int32_t max_sweeps, int32_t max_rounds,
+                               int32_t flags,
+                               const int32_t* merges /* [batch][nc-1][2] or NULL */,
+                               const float* levels   /* [batch][nc-1]    or NULL */,
+                               int32_t* groups  /* [n_rungs][batch][nc] or NULL */,
+                               uint64_t* ut     /* [n_rungs][batch][HDG_RF_SLOTS] */,
+                               int64_t* rq      /* [n_rungs][batch][HDG_RM_Q_SLOTS] */,
+                               void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
