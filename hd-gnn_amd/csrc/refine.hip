@@ -63,6 +63,29 @@
 //            slot is skipped from a register).
 // The round loop is bounded by max_rounds, a group sweep's visits by nc, a chain walk by the
 // slot's size, the total of node sweeps by max_sweeps.
+//
+// hdg_refine_split and hdg_refine_split_ladder are the sweep blocks with rounds whose sweeps a
+// runtime `kinds` chooses (rf_sweep<LADDER, RF_SPLIT>, k_rs_sweep and k_rsl_sweep; the weights
+// launches are again the two above): after the node phase the group sweep above, a split sweep,
+// or one after the other.  A split sweep inside the block (rs_split_sweep), in the LDS arrays
+// the chains use (first, g, t), so no LDS is added:
+//   visit g  skipped without a barrier if g holds fewer than 2 hunks or a split of this sweep
+//            filled it (one flag per slot).  The members are compacted in index order (a
+//            ballot per wave and owned hunk, the waves' counts through LDS).  Seeds: one walk
+//            over the members' rows, every thread keeping the smallest rs_key (gain, p, q) of
+//            its own columns in g; the block minimum through rf_wave_max on the complement.
+//   a step   one member m of a pass: row m, read one member ahead, restricted to the columns
+//            in g; each thread adds the gains of its own hunks to T_G or T_E by the side it
+//            holds for them in a register; wave sums, then one int32 LDS atomic per wave and
+//            side into one of three small buffers used in turn; m's owner puts m's side beside
+//            them; ONE barrier; every thread reads the three words and reaches the same
+//            decision, m's owner records it, and every thread carries C and the size of side
+//            E along.  Thread 0 zeroes the buffer of the step after the next: its readers are
+//            before this step's barrier and its adders behind the next step's.
+//   the cut  if C < 0: the smallest empty slot by a block maximum of keys; every thread
+//            rewrites the slots of its own hunks on side E, thread 0 the two sizes and the flag.
+// A split sweep's visits are bounded by nc, the passes by HDG_RS_PASSES, a pass's steps by the
+// slot's size; every index read from LDS is range-checked before it addresses anything.
 // Integer results only; the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -88,6 +111,14 @@ static_assert((long long)(UT_MAXN / 2) * (UT_MAXN / 2) * (1ll << 19) <= (1ll << 
 static_assert(UT_MAXN <= (1 << 11), "the merge key's tie field holds 11 bits of slot");
 static_assert(41 + 11 <= 64, "the biased merge gain (below 2^41) and the tie field fit one key");
 static_assert((long long)UT_MAXN * (1ll << 16) < (1ll << 31), "a slot's sum of 16-bit parts fits int32");
+// a split sweep (hdg_refine_split): a side sum, the sum between the sides, the seed key
+static_assert((UT_MAXN - 1) * (1ll << 19) < (1ll << 31), "a side sum fits int32");
+static_assert((long long)(UT_MAXN / 2) * (UT_MAXN / 2) * (1ll << 19) <= (1ll << 39),
+              "the sum between the two sides is at most 2^39 in magnitude");
+static_assert(21 + 11 + 11 < 64, "the biased gain (21 bits) and two hunk indices fit one seed key");
+static_assert(HDG_RS_Q_SLOTS == HDG_RM_Q_SLOTS && HDG_RS_Q_SPLITS == HDG_RM_Q_SLOTS - 1,
+              "hdg_refine_split's rq row is hdg_refine_merge's with the last slot in use");
+static_assert(HDG_RS_PASSES >= 1, "a split attempt has its assignment pass");
 
 // workspace, in 4-byte words per commit: the nc x nc matrix of gains, then ut_tiles(nc)
 // no-edge counts, rounded up to an even number of words
@@ -346,21 +377,248 @@ __device__ __forceinline__ uint32_t rm_group_sweep(const int32_t* __restrict__ w
   return merged;
 }
 
+// a seed pair of a split visit as one key: the smaller key wins.  The gain a_pq (|a| <= 2^19,
+// biased by 2^19 into 21 bits), then the lower p, then the lower q.  Below 2^43, so the
+// complement a block maximum goes through is never 0.
+constexpr int32_t RS_BIAS = 1 << 19;
+__device__ __forceinline__ u64 rs_key(const int32_t a, const int p, const int q) {
+  return ((u64)(uint32_t)(a + RS_BIAS) << 22) | ((u64)p << 11) | (u64)q;
+}
+
+__device__ __forceinline__ int32_t rs_wave_sum32(int32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// the block's largest key, in every thread: wave maxima by rf_wave_max, all waves through wkey,
+// which is free on entry and again on return
+__device__ __forceinline__ u64 rs_block_max(u64 key, u64* wkey) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  key = rf_wave_max(key);
+  if (lane == 63) wkey[wave] = key;
+  __syncthreads();
+  u64 best = 0;
+  for (int w = 0; w < RF_WAVES; ++w) best = wkey[w] > best ? wkey[w] : best;
+  __syncthreads();
+  return best;
+}
+
+// One split sweep of hdg_refine_split inside the sweep block (the header's definition), after
+// a node phase or a group sweep: what they wrote need not be behind a barrier yet, and the two
+// buffers of S are left as they are.  mem, filled and scr are the block's first, g and t:
+//   mem      the members of the visited slot, compacted in index order (ballots, wave counts)
+//   filled   per slot: 1 if a split of this sweep filled it
+//   scr      words 0 .. 8: three buffers of (T_G, T_E, the side of m), used in turn by the
+//            steps -- a step adds into buffer st % 3, and after its one barrier thread 0 zeroes
+//            buffer (st + 2) % 3, whose last readers are before that barrier and whose next
+//            adders are behind the next one; words 16 .. 16 + UT_PER * RF_WAVES: the counts
+//            of the compaction
+// A thread keeps the sides of its own hunks in registers (0 not a member or not yet assigned,
+// 1 side G, 2 side E); the side of the step's member m reaches the block through the step's
+// buffer.  C, the sum between the sides, is carried by every thread.  my: this thread's hunks'
+// slots, rewritten by a split.  -> the splits made, uniform; their gains are added to `gain`.
+// On return every write is behind a barrier.
+template <bool LADDER>
+__device__ __forceinline__ uint32_t rs_split_sweep(const int32_t* __restrict__ wb, const float tp,
+                                                   const int nc, int32_t* slot, int32_t* size,
+                                                   int32_t* mem, uint32_t* filled, uint32_t* scr,
+                                                   u64* wkey, int32_t (&my)[UT_PER],
+                                                   long long& gain) {
+  constexpr int CNT = 16;                  // where the compaction's counts start in scr
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int32_t* acc = reinterpret_cast<int32_t*>(scr);
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < UT_PER; ++u) {
+    const int i = tid + u * RF_NT;
+    if (i < nc) filled[i] = 0;
+  }
+  if (tid < 9) acc[tid] = 0;
+  __syncthreads();
+
+  uint32_t splits = 0;
+  uint32_t st = 0;                         // steps made: the buffer of a step is st % 3
+  for (int gv = 0; gv < nc; ++gv) {
+    const int n = size[gv];
+    if (n < 2 || n > nc || filled[gv] != 0) continue;       // uniform
+    // ---- the members of gv in index order ---------------------------------------------------
+    bool in[UT_PER];
+    u64 bal[UT_PER];
+#pragma unroll
+    for (int u = 0; u < UT_PER; ++u) {
+      const int i = tid + u * RF_NT;
+      in[u] = i < nc && my[u] == gv;
+      bal[u] = __ballot(in[u]);
+      if (lane == 0) scr[CNT + u * RF_WAVES + wave] = (uint32_t)__popcll(bal[u]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < UT_PER; ++u) {     // a member's place: the members before it
+      if (!in[u]) continue;
+      uint32_t off = (uint32_t)__popcll(bal[u] & ((1ull << lane) - 1ull));
+      for (int w = 0; w < u * RF_WAVES + wave; ++w) off += scr[CNT + w];
+      if (off < (uint32_t)nc) mem[off] = tid + u * RF_NT;
+    }
+    __syncthreads();
+
+    // ---- seeds: the smallest a_pq over p < q in gv, one walk over the members' rows ---------
+    u64 kmin = ~0ull;
+    {
+      uint32_t m = (uint32_t)mem[0];
+      int32_t pre[UT_PER];
+#pragma unroll
+      for (int u = 0; u < UT_PER; ++u) {
+        const int q = tid + u * RF_NT;
+        pre[u] = (m < (uint32_t)nc && in[u]) ? wb[(size_t)m * nc + q] : 0;
+      }
+      for (int k = 0; k < n && m < (uint32_t)nc; ++k) {
+        const uint32_t mn = k + 1 < n ? (uint32_t)mem[k + 1] : (uint32_t)nc;
+#pragma unroll
+        for (int u = 0; u < UT_PER; ++u) {
+          const int q = tid + u * RF_NT;
+          if (in[u] && q > (int)m) {
+            const u64 key = rs_key(rf_word_gain<LADDER>(pre[u], tp), (int)m, q);
+            kmin = key < kmin ? key : kmin;
+          }
+          pre[u] = (mn < (uint32_t)nc && in[u]) ? wb[(size_t)mn * nc + q] : 0;
+        }
+        m = mn;
+      }
+    }
+    const u64 seed = ~rs_block_max(~kmin, wkey);
+    const int32_t a12 = (int32_t)(uint32_t)(seed >> 22) - RS_BIAS;
+    if (seed == ~0ull || a12 >= 0) continue;                // uniform: no cut of gv can raise Q
+    const int s1 = (int)((seed >> 11) & 2047u), s2 = (int)(seed & 2047u);
+    int32_t sd[UT_PER];
+#pragma unroll
+    for (int u = 0; u < UT_PER; ++u) {
+      const int i = tid + u * RF_NT;
+      sd[u] = i == s1 ? 1 : (i == s2 ? 2 : 0);
+    }
+    long long C = a12;
+    int nE = 1;
+
+    // ---- the assignment pass, then the correction passes ------------------------------------
+    for (int pass = 0; pass < HDG_RS_PASSES; ++pass) {
+      bool changed = false;
+      uint32_t m = (uint32_t)mem[0];
+      int32_t pre[UT_PER];
+#pragma unroll
+      for (int u = 0; u < UT_PER; ++u) {
+        const int q = tid + u * RF_NT;
+        pre[u] = (m < (uint32_t)nc && in[u]) ? wb[(size_t)m * nc + q] : 0;
+      }
+      for (int k = 0; k < n && m < (uint32_t)nc; ++k) {
+        const uint32_t mn = k + 1 < n ? (uint32_t)mem[k + 1] : (uint32_t)nc;
+        int32_t tg = 0, te = 0, mine = 0;
+#pragma unroll
+        for (int u = 0; u < UT_PER; ++u) {
+          const int q = tid + u * RF_NT;
+          const int32_t a = rf_word_gain<LADDER>(pre[u], tp);
+          pre[u] = (mn < (uint32_t)nc && in[u]) ? wb[(size_t)mn * nc + q] : 0;   // the next row
+          if (q == (int)m) mine = sd[u];   // a_mm is 0: m adds nothing to its own side
+          else if (sd[u] == 1) tg += a;
+          else if (sd[u] == 2) te += a;
+        }
+        const bool is_seed = (int)m == s1 || (int)m == s2;  // uniform
+        const uint32_t at = m;
+        m = mn;
+        if (is_seed) continue;
+        int32_t* ab = acc + 3 * (st % 3u);
+        tg = rs_wave_sum32(tg);
+        te = rs_wave_sum32(te);
+        if (lane == 0) {
+          if (tg != 0) atomicAdd(&ab[0], tg);
+          if (te != 0) atomicAdd(&ab[1], te);
+        }
+        if (tid == (int)(at & (uint32_t)(RF_NT - 1))) ab[2] = mine;       // m's owner
+        __syncthreads();
+        const int32_t TG = ab[0], TE = ab[1], X = ab[2];
+        if (tid == 0) {
+          int32_t* az = acc + 3 * ((st + 2u) % 3u);
+          az[0] = az[1] = 0;
+        }
+        ++st;
+        int to = 0;                        // the side m takes, 0: it keeps its own
+        if (pass == 0) {
+          to = TE > TG ? 2 : 1;
+          C += to == 2 ? TG : TE;          // the sum over the other side
+          nE += to == 2;
+        } else {
+          const int32_t own = X == 2 ? TE : TG, other = X == 2 ? TG : TE;
+          if ((X == 1 || X == 2) && other > own) {
+            to = 3 - X;
+            C += (long long)own - (long long)other;
+            nE += to == 2 ? 1 : -1;
+            changed = true;
+          }
+        }
+        if (to != 0) {
+#pragma unroll
+          for (int u = 0; u < UT_PER; ++u)
+            if (tid + u * RF_NT == (int)at) sd[u] = to;
+        }
+      }
+      if (pass > 0 && !changed) break;     // uniform
+    }
+
+    // ---- the decision -----------------------------------------------------------------------
+    if (C < 0) {                           // uniform
+      u64 key = 0;                         // the smallest empty slot
+#pragma unroll
+      for (int u = 0; u < UT_PER; ++u) {
+        const int h = tid + u * RF_NT;
+        if (h < nc && size[h] == 0) {
+          const u64 k = (u64)(UT_MAXN - h);
+          key = k > key ? k : key;
+        }
+      }
+      const u64 best = rs_block_max(key, wkey);
+      if (best != 0 && nE > 0 && nE < n) { // a slot of 2 hunks leaves a slot empty
+        const int e = UT_MAXN - (int)best;
+#pragma unroll
+        for (int u = 0; u < UT_PER; ++u) {
+          const int i = tid + u * RF_NT;
+          if (i < nc && sd[u] == 2) {
+            my[u] = e;
+            slot[i] = e;
+          }
+        }
+        if (tid == 0) {
+          size[e] = nE;
+          size[gv] = n - nE;
+          filled[e] = 1;
+        }
+        ++splits;
+        gain -= C;
+      }
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  return splits;
+}
+
 // The sweep block of both entry points, on one commit (and one rung): wb its matrix, yb its
 // label rows, and groups (or NULL), row and qrow where its outputs go.  The start is gin, the
 // commit's ids (or NULL) -- or with LADDER the cut of the commit's tree (merges, levels; or
 // NULL) at tp, k_cut's unions.  gin and groups may be the same array: a commit's ids are all
 // read before the first barrier and written after the last.
-// With MERGE the sweeps are hdg_refine_merge's rounds (at most max_rounds; a node phase, then
-// one group sweep) and qrow has HDG_RM_Q_SLOTS slots; without it max_rounds is not read.
-template <bool LADDER, bool MERGE>
+// With ROUNDS = RF_MERGE the sweeps are hdg_refine_merge's rounds (at most max_rounds; a node
+// phase, then one group sweep) and qrow has HDG_RM_Q_SLOTS slots; with RF_SPLIT they are
+// hdg_refine_split's (a node phase, then the sweeps `kinds` names: a group sweep, a split sweep);
+// with RF_PLAIN neither max_rounds nor kinds is read.
+constexpr int RF_PLAIN = 0, RF_MERGE = 1, RF_SPLIT = 2;
+template <bool LADDER, int ROUNDS>
 __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
                                          const uint32_t* __restrict__ yb, const int32_t* gin,
                                          const int32_t* __restrict__ merges,
                                          const float* __restrict__ levels, const float tp,
                                          int32_t* groups, u64* __restrict__ row,
                                          long long* __restrict__ qrow, const int nc,
-                                         const int max_sweeps, const int max_rounds) {
+                                         const int max_sweeps, const int max_rounds,
+                                         const int kinds) {
   __shared__ int32_t S[2][UT_MAXN];        // the per-slot sums of this step and the next
   __shared__ int32_t slot[UT_MAXN];
   __shared__ int32_t size[UT_MAXN];
@@ -451,8 +709,8 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
   int cur = 0, sweeps = 0, converged = 0;
   uint32_t moves = 0;
   long long gain = 0;
-  int rounds = 0;                          // MERGE: group sweeps run, their merges, and the
-  uint32_t nmerged = 0;                    // gain of the first node phase
+  int rounds = 0;                          // with rounds: those run, their merges and splits,
+  uint32_t nmerged = 0, nsplit = 0;        // and the gain of the first node phase
   long long node_gain = 0;
   for (int sw = 0; sw < max_sweeps; ++sw) {
     bool moved = false;
@@ -514,7 +772,7 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
       cur ^= 1;
     }
     ++sweeps;
-    if constexpr (MERGE) {                 // a node phase ends here: one group sweep, a round
+    if constexpr (ROUNDS == RF_MERGE) {    // a node phase ends here: one group sweep, a round
       if (moved && sweeps < max_sweeps) continue;
       if (rounds == 0) node_gain = gain;
       const uint32_t merged =
@@ -523,6 +781,20 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
       ++rounds;
       converged = !moved && merged == 0;
       if (merged == 0 || rounds >= max_rounds) break;      // or the sweeps are used up
+    } else if constexpr (ROUNDS == RF_SPLIT) {              // ... then the sweeps of `kinds`
+      if (moved && sweeps < max_sweeps) continue;
+      if (rounds == 0) node_gain = gain;
+      uint32_t merged = 0, split = 0;      // kinds is uniform
+      if (kinds & HDG_RS_MERGE)
+        merged = rm_group_sweep<LADDER>(wb, tp, nc, nwav, S, slot, size, first, g, t, wkey, my,
+                                        gain);
+      if (kinds & HDG_RS_SPLIT)
+        split = rs_split_sweep<LADDER>(wb, tp, nc, slot, size, first, g, t, wkey, my, gain);
+      nmerged += merged;
+      nsplit += split;
+      ++rounds;
+      converged = !moved && merged == 0 && split == 0;
+      if ((merged == 0 && split == 0) || rounds >= max_rounds) break;
     } else if (!moved) {
       converged = 1;
       break;
@@ -560,11 +832,11 @@ __device__ __forceinline__ void rf_sweep(const int32_t* __restrict__ wb,
     qrow[HDG_RF_Q_END] = q_start + gain;
     qrow[HDG_RF_Q_SWEEPS] = sweeps;
     qrow[HDG_RF_Q_CONVERGED] = converged;
-    if constexpr (MERGE) {
+    if constexpr (ROUNDS != RF_PLAIN) {
       qrow[HDG_RM_Q_ROUNDS] = rounds;
       qrow[HDG_RM_Q_MERGES] = nmerged;
       qrow[HDG_RM_Q_NODE] = q_start + node_gain;
-      qrow[HDG_RM_Q_SLOTS - 1] = 0;
+      qrow[HDG_RS_Q_SPLITS] = nsplit;      // 0 without split sweeps
     }
   }
 }
@@ -576,9 +848,9 @@ __global__ __launch_bounds__(RF_NT) void k_rf_sweep(const int32_t* __restrict__ 
                                                     long long* __restrict__ rq, const int nc,
                                                     const int max_sweeps) {
   const size_t b = blockIdx.x;
-  rf_sweep<false, false>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+  rf_sweep<false, RF_PLAIN>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
                          gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
-                         ut + b * HDG_RF_SLOTS, rq + b * HDG_RF_Q_SLOTS, nc, max_sweeps, 1);
+                         ut + b * HDG_RF_SLOTS, rq + b * HDG_RF_Q_SLOTS, nc, max_sweeps, 1, 0);
 }
 
 // hdg_refine_merge: k_rf_sweep's block with rounds; rq rows of HDG_RM_Q_SLOTS
@@ -589,10 +861,10 @@ __global__ __launch_bounds__(RF_NT) void k_rm_sweep(const int32_t* __restrict__ 
                                                     long long* __restrict__ rq, const int nc,
                                                     const int max_sweeps, const int max_rounds) {
   const size_t b = blockIdx.x;
-  rf_sweep<false, true>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+  rf_sweep<false, RF_MERGE>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
                         gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
                         ut + b * HDG_RF_SLOTS, rq + b * HDG_RM_Q_SLOTS, nc, max_sweeps,
-                        max_rounds);
+                        max_rounds, HDG_RS_MERGE);
 }
 
 // grid (rungs, B): the rungs of a commit are dispatched together and share its matrix in L2;
@@ -607,11 +879,11 @@ __global__ __launch_bounds__(RF_NT) void k_rl_sweep(const int32_t* __restrict__ 
                                                     const int max_sweeps) {
   const size_t b = blockIdx.y, o = (size_t)blockIdx.x * gridDim.y + b;
   const size_t n1 = (size_t)nc - 1;
-  rf_sweep<true, false>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
+  rf_sweep<true, RF_PLAIN>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
                         merges ? merges + b * n1 * 2 : nullptr,
                         merges ? levels + b * n1 : nullptr, bounds.tp[blockIdx.x],
                         groups ? groups + o * nc : nullptr, ut + o * HDG_RF_SLOTS,
-                        rq + o * HDG_RF_Q_SLOTS, nc, max_sweeps, 1);
+                        rq + o * HDG_RF_Q_SLOTS, nc, max_sweeps, 1, 0);
 }
 
 // hdg_refine_merge_ladder: k_rl_sweep's block with rounds; rq rows of HDG_RM_Q_SLOTS
@@ -625,17 +897,54 @@ __global__ __launch_bounds__(RF_NT) void k_rml_sweep(const int32_t* __restrict__
                                                      const int max_sweeps, const int max_rounds) {
   const size_t b = blockIdx.y, o = (size_t)blockIdx.x * gridDim.y + b;
   const size_t n1 = (size_t)nc - 1;
-  rf_sweep<true, true>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
+  rf_sweep<true, RF_MERGE>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc), nullptr,
                        merges ? merges + b * n1 * 2 : nullptr,
                        merges ? levels + b * n1 : nullptr, bounds.tp[blockIdx.x],
                        groups ? groups + o * nc : nullptr, ut + o * HDG_RF_SLOTS,
-                       rq + o * HDG_RM_Q_SLOTS, nc, max_sweeps, max_rounds);
+                       rq + o * HDG_RM_Q_SLOTS, nc, max_sweeps, max_rounds,
+                       HDG_RS_MERGE);
 }
 
-// what the four entry points check first, in this order.  max_rounds: NULL for the calls
-// without rounds
+// hdg_refine_split: k_rm_sweep's block, a round's sweeps chosen by `kinds`; rq rows of
+// HDG_RS_Q_SLOTS
+__global__ __launch_bounds__(RF_NT) void k_rs_sweep(const int32_t* __restrict__ ws,
+                                                    const uint32_t* __restrict__ ybits,
+                                                    const int32_t* gin, int32_t* groups,
+                                                    u64* __restrict__ ut,
+                                                    long long* __restrict__ rq, const int nc,
+                                                    const int max_sweeps, const int max_rounds,
+                                                    const int kinds) {
+  const size_t b = blockIdx.x;
+  rf_sweep<false, RF_SPLIT>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+                            gin ? gin + b * nc : nullptr, nullptr, nullptr, 0.f, groups + b * nc,
+                            ut + b * HDG_RF_SLOTS, rq + b * HDG_RS_Q_SLOTS, nc, max_sweeps,
+                            max_rounds, kinds);
+}
+
+// hdg_refine_split_ladder: k_rml_sweep's block, a round's sweeps chosen by `kinds`
+__global__ __launch_bounds__(RF_NT) void k_rsl_sweep(const int32_t* __restrict__ ws,
+                                                     const uint32_t* __restrict__ ybits,
+                                                     const int32_t* __restrict__ merges,
+                                                     const float* __restrict__ levels,
+                                                     const rl_bounds bounds, int32_t* groups,
+                                                     u64* __restrict__ ut,
+                                                     long long* __restrict__ rq, const int nc,
+                                                     const int max_sweeps, const int max_rounds,
+                                                     const int kinds) {
+  const size_t b = blockIdx.y, o = (size_t)blockIdx.x * gridDim.y + b;
+  const size_t n1 = (size_t)nc - 1;
+  rf_sweep<true, RF_SPLIT>(ws + b * rf_commit_words(nc), ut_label_rows(ybits, (int)b, nc),
+                           nullptr, merges ? merges + b * n1 * 2 : nullptr,
+                           merges ? levels + b * n1 : nullptr, bounds.tp[blockIdx.x],
+                           groups ? groups + o * nc : nullptr, ut + o * HDG_RF_SLOTS,
+                           rq + o * HDG_RS_Q_SLOTS, nc, max_sweeps, max_rounds, kinds);
+}
+
+// what the six entry points check first, in this order.  max_rounds: NULL for the calls
+// without rounds; kinds: NULL for the calls that are not hdg_refine_split's
 inline int rf_check_call(const hdg_shape* s, const int32_t rule, const int32_t max_sweeps,
-                         const int32_t* max_rounds, const int32_t flags, const char* who) {
+                         const int32_t* max_rounds, const int32_t* kinds, const int32_t flags,
+                         const char* who) {
   if (const int rc = ut_check_shape(s, who)) return rc;
   if (const int rc = ut_check_rule(rule, who)) return rc;
   if (max_sweeps < 1 || max_sweeps > HDG_RF_MAX_SWEEPS)
@@ -644,17 +953,21 @@ inline int rf_check_call(const hdg_shape* s, const int32_t rule, const int32_t m
   if (max_rounds && (*max_rounds < 1 || *max_rounds > HDG_RM_MAX_ROUNDS))
     return fail(HDG_EINVAL, "%s: max_rounds must be in [1, %d] (got %d)", who, HDG_RM_MAX_ROUNDS,
                 (int)*max_rounds);
+  if (kinds && (*kinds < 1 || *kinds > (HDG_RS_MERGE | HDG_RS_SPLIT)))
+    return fail(HDG_EINVAL, "%s: kinds must be HDG_RS_MERGE, HDG_RS_SPLIT or both (got %d)", who,
+                (int)*kinds);
   if (flags != 0) return fail(HDG_EINVAL, "%s: unknown flag bits 0x%x", who, (unsigned)flags);
   return 0;
 }
 
-// hdg_refine (max_rounds NULL) and hdg_refine_merge under the name `who`: the checks, the
-// weights launch, the sweep launch
+// hdg_refine (max_rounds NULL), hdg_refine_merge (kinds NULL) and hdg_refine_split under the
+// name `who`: the checks, the weights launch, the sweep launch
 int rf_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const float* probs,
             const float threshold, const int32_t rule, const int32_t max_sweeps,
-            const int32_t* max_rounds, const int32_t flags, const int32_t* groups_in,
+            const int32_t* max_rounds, const int32_t* kinds, const int32_t flags,
+            const int32_t* groups_in,
             int32_t* groups, uint64_t* ut, int64_t* rq, void* workspace, void* stream) {
-  if (const int rc = rf_check_call(s, rule, max_sweeps, max_rounds, flags, who)) return rc;
+  if (const int rc = rf_check_call(s, rule, max_sweeps, max_rounds, kinds, flags, who)) return rc;
   const float tp = ut_link_bound(rule, threshold);
   if (!std::isfinite(threshold) || !std::isfinite(tp))
     return fail(HDG_EINVAL, "%s: threshold %g gives no finite link bound", who,
@@ -668,7 +981,11 @@ int rf_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const floa
   hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)ut_tiles(nc), (unsigned)s->batch),
                      dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule, tp);
   if (const int rc = ut_launched(who, "weights")) return rc;
-  if (max_rounds)
+  if (kinds)
+    hipLaunchKernelGGL(k_rs_sweep, dim3((unsigned)s->batch), dim3(RF_NT), 0, st,
+                       (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
+                       (long long*)rq, nc, (int)max_sweeps, (int)*max_rounds, (int)*kinds);
+  else if (max_rounds)
     hipLaunchKernelGGL(k_rm_sweep, dim3((unsigned)s->batch), dim3(RF_NT), 0, st,
                        (const int32_t*)workspace, bt->ybits, groups_in, groups, (u64*)ut,
                        (long long*)rq, nc, (int)max_sweeps, (int)*max_rounds);
@@ -679,13 +996,14 @@ int rf_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const floa
   return ut_launched(who, "sweep");
 }
 
-// hdg_refine_ladder (max_rounds NULL) and hdg_refine_merge_ladder under the name `who`
+// hdg_refine_ladder (max_rounds NULL), hdg_refine_merge_ladder (kinds NULL) and
+// hdg_refine_split_ladder under the name `who`
 int rl_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const float* probs,
             const float* thresholds, const int32_t n_rungs, const int32_t rule,
-            const int32_t max_sweeps, const int32_t* max_rounds, const int32_t flags,
-            const int32_t* merges, const float* levels, int32_t* groups, uint64_t* ut,
+            const int32_t max_sweeps, const int32_t* max_rounds, const int32_t* kinds,
+            const int32_t flags, const int32_t* merges, const float* levels, int32_t* groups, uint64_t* ut,
             int64_t* rq, void* workspace, void* stream) {
-  if (const int rc = rf_check_call(s, rule, max_sweeps, max_rounds, flags, who)) return rc;
+  if (const int rc = rf_check_call(s, rule, max_sweeps, max_rounds, kinds, flags, who)) return rc;
   if (n_rungs < 1 || n_rungs > HDG_RL_MAX_RUNGS)
     return fail(HDG_EINVAL, "%s: n_rungs must be in [1, %d] (got %d)", who, HDG_RL_MAX_RUNGS,
                 (int)n_rungs);
@@ -709,7 +1027,11 @@ int rl_call(const char* who, const hdg_shape* s, const hdg_batch* bt, const floa
                      dim3(UT_LINK_NT), 0, st, probs, (int32_t*)workspace, nc, (int)rule);
   if (const int rc = ut_launched(who, "weights")) return rc;
   const dim3 grid((unsigned)n_rungs, (unsigned)s->batch);
-  if (max_rounds)
+  if (kinds)
+    hipLaunchKernelGGL(k_rsl_sweep, grid, dim3(RF_NT), 0, st, (const int32_t*)workspace,
+                       bt->ybits, merges, levels, bounds, groups, (u64*)ut, (long long*)rq, nc,
+                       (int)max_sweeps, (int)*max_rounds, (int)*kinds);
+  else if (max_rounds)
     hipLaunchKernelGGL(k_rml_sweep, grid, dim3(RF_NT), 0, st, (const int32_t*)workspace,
                        bt->ybits, merges, levels, bounds, groups, (u64*)ut, (long long*)rq, nc,
                        (int)max_sweeps, (int)*max_rounds);
@@ -732,8 +1054,8 @@ extern "C" int hdg_refine(const hdg_shape* s, const hdg_batch* bt, const float* 
                           float threshold, int32_t rule, int32_t max_sweeps, int32_t flags,
                           const int32_t* groups_in, int32_t* groups, uint64_t* ut, int64_t* rq,
                           void* workspace, void* stream) {
-  return rf_call("hdg_refine", s, bt, probs, threshold, rule, max_sweeps, nullptr, flags,
-                 groups_in, groups, ut, rq, workspace, stream);
+  return rf_call("hdg_refine", s, bt, probs, threshold, rule, max_sweeps, nullptr, nullptr,
+                 flags, groups_in, groups, ut, rq, workspace, stream);
 }
 
 extern "C" int hdg_refine_merge(const hdg_shape* s, const hdg_batch* bt, const float* probs,
@@ -742,7 +1064,7 @@ extern "C" int hdg_refine_merge(const hdg_shape* s, const hdg_batch* bt, const f
                                 int32_t* groups, uint64_t* ut, int64_t* rq, void* workspace,
                                 void* stream) {
   return rf_call("hdg_refine_merge", s, bt, probs, threshold, rule, max_sweeps, &max_rounds,
-                 flags, groups_in, groups, ut, rq, workspace, stream);
+                 nullptr, flags, groups_in, groups, ut, rq, workspace, stream);
 }
 
 extern "C" size_t hdg_refine_ladder_workspace_bytes(const hdg_shape* s, int32_t flags) {
@@ -757,7 +1079,7 @@ extern "C" int hdg_refine_ladder(const hdg_shape* s, const hdg_batch* bt, const 
                                  const float* levels, int32_t* groups, uint64_t* ut, int64_t* rq,
                                  void* workspace, void* stream) {
   return rl_call("hdg_refine_ladder", s, bt, probs, thresholds, n_rungs, rule, max_sweeps,
-                 nullptr, flags, merges, levels, groups, ut, rq, workspace, stream);
+                 nullptr, nullptr, flags, merges, levels, groups, ut, rq, workspace, stream);
 }
 
 extern "C" int hdg_refine_merge_ladder(const hdg_shape* s, const hdg_batch* bt,
@@ -767,5 +1089,25 @@ extern "C" int hdg_refine_merge_ladder(const hdg_shape* s, const hdg_batch* bt,
                                        const float* levels, int32_t* groups, uint64_t* ut,
                                        int64_t* rq, void* workspace, void* stream) {
   return rl_call("hdg_refine_merge_ladder", s, bt, probs, thresholds, n_rungs, rule, max_sweeps,
-                 &max_rounds, flags, merges, levels, groups, ut, rq, workspace, stream);
+                 &max_rounds, nullptr, flags, merges, levels, groups, ut, rq, workspace, stream);
+}
+
+extern "C" int hdg_refine_split(const hdg_shape* s, const hdg_batch* bt, const float* probs,
+                                float threshold, int32_t rule, int32_t max_sweeps,
+                                int32_t max_rounds, int32_t kinds, int32_t flags,
+                                const int32_t* groups_in, int32_t* groups, uint64_t* ut,
+                                int64_t* rq, void* workspace, void* stream) {
+  return rf_call("hdg_refine_split", s, bt, probs, threshold, rule, max_sweeps, &max_rounds,
+                 &kinds, flags, groups_in, groups, ut, rq, workspace, stream);
+}
+
+extern "C" int hdg_refine_split_ladder(const hdg_shape* s, const hdg_batch* bt,
+                                       const float* probs, const float* thresholds,
+                                       int32_t n_rungs, int32_t rule, int32_t max_sweeps,
+                                       int32_t max_rounds, int32_t kinds, int32_t flags,
+                                       const int32_t* merges, const float* levels,
+                                       int32_t* groups, uint64_t* ut, int64_t* rq,
+                                       void* workspace, void* stream) {
+  return rl_call("hdg_refine_split_ladder", s, bt, probs, thresholds, n_rungs, rule, max_sweeps,
+                 &max_rounds, &kinds, flags, merges, levels, groups, ut, rq, workspace, stream);
 }

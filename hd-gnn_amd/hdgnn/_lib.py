@@ -90,6 +90,12 @@ RL_MAX_RUNGS = 64
 RM_Q_SLOTS = 8
 RM_Q_ROUNDS, RM_Q_MERGES, RM_Q_NODE = 4, 5, 6
 RM_MAX_ROUNDS = 16
+# hdg_refine_split / hdg_refine_split_ladder: the kinds of sweep a round runs, the passes of one
+# split attempt, rq rows of RS_Q_SLOTS i64 (slots 0 .. 6 as RM_Q_*)
+RS_MERGE, RS_SPLIT = 1, 2
+RS_KINDS = {"merge": RS_MERGE, "split": RS_SPLIT, "both": RS_MERGE | RS_SPLIT}
+RS_PASSES = 4
+RS_Q_SLOTS, RS_Q_SPLITS = 8, 7
 
 
 def untangle_blocks(nc):
@@ -119,7 +125,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_agglomerate_workspace_bytes", "hdg_agglomerate", "hdg_cut",
            "hdg_refine_workspace_bytes", "hdg_refine",
            "hdg_refine_ladder_workspace_bytes", "hdg_refine_ladder",
-           "hdg_refine_merge", "hdg_refine_merge_ladder"]
+           "hdg_refine_merge", "hdg_refine_merge_ladder",
+           "hdg_refine_split", "hdg_refine_split_ladder"]
 
 _lib = None
 
@@ -181,6 +188,10 @@ def load(path=None):
                                      vp, vp, vp]
     lib.hdg_refine_merge_ladder.argtypes = [P(Shape), P(Batch), vp, P(f32), i32, i32, i32, i32,
                                             i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.hdg_refine_split.argtypes = [P(Shape), P(Batch), vp, f32, i32, i32, i32, i32, i32, vp, vp,
+                                     vp, vp, vp, vp]
+    lib.hdg_refine_split_ladder.argtypes = [P(Shape), P(Batch), vp, P(f32), i32, i32, i32, i32,
+                                            i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

@@ -557,8 +557,35 @@ class Engine:
                              % (_lib.RM_MAX_ROUNDS, max_rounds))
         return self._refine(dbatch, groups, probs, threshold, rule, max_sweeps, max_rounds)
 
-    def _refine(self, dbatch, groups, probs, threshold, rule, max_sweeps, max_rounds):
-        """refine() (max_rounds None) and refine_merge(): the checks, the outputs, the call."""
+    def refine_split(self, dbatch, groups=None, probs=None, threshold=0.5, rule="mean",
+                     max_sweeps=8, max_rounds=4, kinds="both"):
+        """hdg_refine_split: refine_merge()'s rounds with the sweeps `kinds` names after every
+        node phase -- "merge": the group sweep alone (refine_merge() itself), "split": one split
+        sweep, in which a group is cut in two from two seeds if the sum between the two sides is
+        below 0 (include/hdgnn.h), "both": the group sweep, then the split sweep -> (groups
+        int32 [B][nc], ut int64 [B][RF_SLOTS], rq int64 [B][RS_Q_SLOTS]) as fresh device
+        tensors: refine_merge()'s, with the accepted splits in rq's last slot.  Arguments,
+        stream and workspace as refine()'s."""
+        return self._refine(dbatch, groups, probs, threshold, rule, max_sweeps,
+                            self._rounds(max_rounds), self._kinds(kinds))
+
+    @staticmethod
+    def _rounds(max_rounds):
+        if not (isinstance(max_rounds, int) and 1 <= max_rounds <= _lib.RM_MAX_ROUNDS):
+            raise ValueError("max_rounds must be an int in [1, %d] (got %r)"
+                             % (_lib.RM_MAX_ROUNDS, max_rounds))
+        return max_rounds
+
+    @staticmethod
+    def _kinds(kinds):
+        if not (isinstance(kinds, str) and kinds in _lib.RS_KINDS):
+            raise ValueError("kinds must be one of %s (got %r)"
+                             % (", ".join(_lib.RS_KINDS), kinds))
+        return _lib.RS_KINDS[kinds]
+
+    def _refine(self, dbatch, groups, probs, threshold, rule, max_sweeps, max_rounds, kinds=None):
+        """refine() (max_rounds None), refine_merge() (kinds None) and refine_split(): the
+        checks, the outputs, the call."""
         self._check(dbatch)
         probs = self._decode_probs(probs)
         rule = self._rule(rule)
@@ -579,7 +606,8 @@ class Engine:
                          dtype=torch.int64, device=self.device)
         b = dbatch.struct()
         call, budget = ((self.lib.hdg_refine, (max_sweeps,)) if max_rounds is None
-                        else (self.lib.hdg_refine_merge, (max_sweeps, max_rounds)))
+                        else (self.lib.hdg_refine_merge, (max_sweeps, max_rounds)) if kinds is None
+                        else (self.lib.hdg_refine_split, (max_sweeps, max_rounds, kinds)))
         _lib.check(call(ctypes.byref(self.shape), ctypes.byref(b),
                         ctypes.c_void_p(probs.data_ptr()), ctypes.c_float(threshold), rule,
                         *budget, 0,
@@ -614,9 +642,19 @@ class Engine:
         return self._refine_ladder(dbatch, thresholds, tree, probs, rule, max_sweeps, max_rounds,
                                    groups)
 
-    def _refine_ladder(self, dbatch, thresholds, tree, probs, rule, max_sweeps, max_rounds, groups):
-        """refine_ladder() (max_rounds None) and refine_merge_ladder(): the checks, the
-        outputs, the call."""
+    def refine_split_ladder(self, dbatch, thresholds, tree=None, probs=None, rule="mean",
+                            max_sweeps=8, max_rounds=4, kinds="both", groups=False):
+        """hdg_refine_split_ladder: refine_merge_ladder() with refine_split()'s rounds at every
+        rung -> (ut int64 [T][B][RF_SLOTS], rq int64 [T][B][RS_Q_SLOTS], groups int32
+        [T][B][nc] or None unless `groups`): rung k holds what cut() then refine_split() at
+        thresholds[k] return.  Arguments, stream and workspace as refine_ladder()'s."""
+        return self._refine_ladder(dbatch, thresholds, tree, probs, rule, max_sweeps,
+                                   self._rounds(max_rounds), groups, self._kinds(kinds))
+
+    def _refine_ladder(self, dbatch, thresholds, tree, probs, rule, max_sweeps, max_rounds, groups,
+                       kinds=None):
+        """refine_ladder() (max_rounds None), refine_merge_ladder() (kinds None) and
+        refine_split_ladder(): the checks, the outputs, the call."""
         self._check(dbatch)
         probs = self._decode_probs(probs)
         rule = self._rule(rule)
@@ -654,7 +692,9 @@ class Engine:
                          dtype=torch.int64, device=self.device)
         b = dbatch.struct()
         call, budget = ((self.lib.hdg_refine_ladder, (max_sweeps,)) if max_rounds is None
-                        else (self.lib.hdg_refine_merge_ladder, (max_sweeps, max_rounds)))
+                        else (self.lib.hdg_refine_merge_ladder, (max_sweeps, max_rounds))
+                        if kinds is None
+                        else (self.lib.hdg_refine_split_ladder, (max_sweeps, max_rounds, kinds)))
         _lib.check(call(
             ctypes.byref(self.shape), ctypes.byref(b), ctypes.c_void_p(probs.data_ptr()),
             (ctypes.c_float * T)(*thr), T, rule, *budget, 0,

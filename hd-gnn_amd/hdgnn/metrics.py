@@ -681,9 +681,59 @@ def _group_sweep(A, slot, size):
     return merges, gain
 
 
-def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds):
-    """refine (max_rounds None) and refine_merge: the checks, the start, the node phase --
-    alone, or in rounds with a group sweep after each -- and the rows."""
+def _split_sweep(A, slot, size):
+    """One split sweep of hdg_refine_split (include/hdgnn.h) on one commit's gains A, in place
+    on slot and size -> (splits, gain in Q).  Per visit of a slot g of at least 2 hunks that no
+    split of this sweep filled: the seeds (the pair of g with the smallest gain, the lowest p
+    then the lowest q among equals; nothing happens unless it is below 0), the assignment pass,
+    at most RS_PASSES - 1 correction passes, and the cut is taken iff the sum between the two
+    sides is below 0: side E moves to the smallest empty slot."""
+    nc = len(slot)
+    splits = gain = 0
+    filled = np.zeros(nc, bool)
+    for g in range(nc):
+        if size[g] < 2 or filled[g]:
+            continue
+        mem = np.flatnonzero(slot == g)                    # index order
+        n = len(mem)
+        sub = A[np.ix_(mem, mem)]                          # int64, 0 on the diagonal
+        iu, ju = np.triu_indices(n, 1)                     # p ascending, then q ascending
+        k = int(np.argmin(sub[iu, ju]))                    # the first among equals
+        s1, s2 = int(iu[k]), int(ju[k])
+        if sub[s1, s2] >= 0:
+            continue
+        side = np.zeros(n, np.int64)                       # 0 not assigned, 1 side G, 2 side E
+        side[s1], side[s2] = 1, 2
+        others = [m for m in range(n) if m != s1 and m != s2]
+        for m in others:
+            side[m] = 2 if sub[m, side == 2].sum() > sub[m, side == 1].sum() else 1
+        for _ in range(RS_PASSES - 1):
+            changed = False
+            for m in others:
+                x = side[m]
+                if sub[m, side == 3 - x].sum() > sub[m, side == x].sum():      # a_mm is 0
+                    side[m] = 3 - x
+                    changed = True
+            if not changed:
+                break
+        C = int(sub[np.ix_(side == 1, side == 2)].sum())
+        if C >= 0:
+            continue
+        e = int(np.flatnonzero(size == 0)[0])
+        moved = mem[side == 2]
+        slot[moved] = e
+        size[e] = len(moved)
+        size[g] -= len(moved)
+        filled[e] = True
+        gain -= C
+        splits += 1
+    return splits, gain
+
+
+def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds, kinds=1):
+    """refine (max_rounds None), refine_merge and refine_split: the checks, the start, the node
+    phase -- alone, or in rounds with the sweeps of `kinds` (1 a group sweep, 2 a split sweep,
+    3 both) after each -- and the rows."""
     from .data import pair_index
     if rule not in UT_RULES:
         raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
@@ -696,6 +746,8 @@ def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds
         raise ValueError("max_sweeps must be in [1, %d] (got %r)" % (RF_MAX_SWEEPS, max_sweeps))
     if max_rounds is not None and not 1 <= int(max_rounds) <= RM_MAX_ROUNDS:
         raise ValueError("max_rounds must be in [1, %d] (got %r)" % (RM_MAX_ROUNDS, max_rounds))
+    if kinds not in (RS_MERGE, RS_SPLIT, RS_MERGE | RS_SPLIT):
+        raise ValueError("kinds must be 1 (merge), 2 (split) or 3 (both) (got %r)" % (kinds,))
     label = np.asarray(label_onehot)
     probs = np.asarray(probs, np.float32)
     B, R = probs.shape[0], probs.shape[2]
@@ -722,14 +774,21 @@ def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds
         moves, sweeps, conv, gain = _node_phase(A, slot, size, int(max_sweeps))
         q1 = q0 + gain
         if max_rounds is not None:
-            rounds, merges, qn = 0, 0, q1
+            rounds, merges, splits, qn = 0, 0, 0, q1
             while True:
-                merged, gain = _group_sweep(A, slot, size)
+                merged = split = 0
+                if kinds & RS_MERGE:
+                    merged, gain = _group_sweep(A, slot, size)
+                    q1 += gain
+                if kinds & RS_SPLIT:
+                    split, gain = _split_sweep(A, slot, size)
+                    q1 += gain
                 rounds += 1
                 merges += merged
-                q1 += gain
-                conv = int(conv and not merged)
-                if not merged or rounds >= int(max_rounds) or sweeps >= int(max_sweeps):
+                splits += split
+                acted = merged + split
+                conv = int(conv and not acted)
+                if not acted or rounds >= int(max_rounds) or sweeps >= int(max_sweeps):
                     break
                 m, s, conv, gain = _node_phase(A, slot, size, int(max_sweeps) - sweeps)
                 moves, sweeps, q1 = moves + m, sweeps + s, q1 + gain
@@ -747,7 +806,7 @@ def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds
                  np.count_nonzero(~sp & ~st), moves, nans)
         rq[b, :RF_Q_SLOTS] = (q0, q1, sweeps, conv)
         if max_rounds is not None:
-            rq[b, RF_Q_SLOTS:] = (rounds, merges, qn, 0)
+            rq[b, RF_Q_SLOTS:] = (rounds, merges, qn, splits)
     return ut, out, rq
 
 
@@ -759,6 +818,10 @@ def _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds
 RM_Q_SLOTS = 8
 RM_Q_ROUNDS, RM_Q_MERGES, RM_Q_NODE = 4, 5, 6
 RM_MAX_ROUNDS = 16
+# hdg_refine_split: the kinds of sweep of a round, the passes of a split attempt, the rq row
+RS_MERGE, RS_SPLIT = 1, 2
+RS_PASSES = 4
+RS_Q_SLOTS, RS_Q_SPLITS = 8, 7
 
 
 def refine_merge(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8,
@@ -773,6 +836,20 @@ def refine_merge(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sw
     if max_rounds is None:
         raise ValueError("max_rounds must be in [1, %d] (got None)" % RM_MAX_ROUNDS)
     return _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds)
+
+
+def refine_split(label_onehot, probs, groups, threshold=0.5, rule="mean", max_sweeps=8,
+                 max_rounds=4, kinds=3):
+    """refine_merge() with split sweeps -> (ut int64 (B, RF_SLOTS), groups int32 (B, Nc), rq
+    int64 (B, RS_Q_SLOTS)): the host restatement of hdg_refine_split, definitions as in
+    include/hdgnn.h.  A round is refine's node phase, then with kinds & RS_MERGE one group sweep
+    and with kinds & RS_SPLIT one split sweep (_split_sweep: seeded bisection of a slot, taken
+    iff the sum between the two sides is below 0); until a round merges nothing and splits
+    nothing, `max_rounds` rounds have run or the node sweeps reach `max_sweeps`.  rq is
+    refine_merge's row with the accepted splits in RS_Q_SPLITS."""
+    if max_rounds is None:
+        raise ValueError("max_rounds must be in [1, %d] (got None)" % RM_MAX_ROUNDS)
+    return _refine(label_onehot, probs, groups, threshold, rule, max_sweeps, max_rounds, kinds)
 
 
 # ---------------------------------------------------------------------------------------
@@ -810,17 +887,8 @@ def refine_ladder(label_onehot, probs, thresholds, tree=None, rule="mean", max_s
     any merge tree or None -> (ut int64 (T, B, RF_SLOTS), groups int32 (T, B, Nc), rq int64
     (T, B, RF_Q_SLOTS)): the host restatement of hdg_refine_ladder.  A loop: per rung
     cut_groups at the rung's link bound (None: every hunk alone), then refine at the rung."""
-    thr = _rungs(thresholds)
-    if rule not in UT_RULES:
-        raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
-    out = []
-    for t in thr:
-        start = None
-        if tree is not None:
-            with np.errstate(over="ignore"):
-                start = cut_groups(tree[0], tree[1], t + t if rule == "mean" else t)
-        out.append(refine(label_onehot, probs, start, t, rule, max_sweeps))
-    return tuple(np.stack([o[i] for o in out]) for i in range(3))
+    return _ladder_of(lambda start, t: refine(label_onehot, probs, start, t, rule, max_sweeps),
+                      thresholds, tree, rule)
 
 
 def refine_merge_ladder(label_onehot, probs, thresholds, tree=None, rule="mean", max_sweeps=8,
@@ -829,6 +897,25 @@ def refine_merge_ladder(label_onehot, probs, thresholds, tree=None, rule="mean",
     int64 (T, B, RM_Q_SLOTS)): the host restatement of hdg_refine_merge_ladder.  A loop: per
     rung cut_groups at the rung's link bound (None: every hunk alone), then refine_merge at
     the rung."""
+    return _ladder_of(lambda start, t: refine_merge(label_onehot, probs, start, t, rule,
+                                                    max_sweeps, max_rounds),
+                      thresholds, tree, rule)
+
+
+def refine_split_ladder(label_onehot, probs, thresholds, tree=None, rule="mean", max_sweeps=8,
+                        max_rounds=4, kinds=3):
+    """refine_merge_ladder() with refine_split()'s rounds -> (ut int64 (T, B, RF_SLOTS), groups
+    int32 (T, B, Nc), rq int64 (T, B, RS_Q_SLOTS)): the host restatement of
+    hdg_refine_split_ladder.  A loop: per rung cut_groups at the rung's link bound (None: every
+    hunk alone), then refine_split at the rung."""
+    return _ladder_of(lambda start, t: refine_split(label_onehot, probs, start, t, rule,
+                                                    max_sweeps, max_rounds, kinds),
+                      thresholds, tree, rule)
+
+
+def _ladder_of(run, thresholds, tree, rule):
+    """The loop of every ladder: per rung the cut of `tree` at the rung's link bound
+    (None: every hunk alone), then run(start, threshold); the rungs stacked."""
     thr = _rungs(thresholds)
     if rule not in UT_RULES:
         raise ValueError("rule must be one of %s (got %r)" % (", ".join(UT_RULES), rule))
@@ -838,7 +925,7 @@ def refine_merge_ladder(label_onehot, probs, thresholds, tree=None, rule="mean",
         if tree is not None:
             with np.errstate(over="ignore"):
                 start = cut_groups(tree[0], tree[1], t + t if rule == "mean" else t)
-        out.append(refine_merge(label_onehot, probs, start, t, rule, max_sweeps, max_rounds))
+        out.append(run(start, t))
     return tuple(np.stack([o[i] for o in out]) for i in range(3))
 
 

@@ -607,9 +607,18 @@ class graph2graph(object):
         if merge and refine < 1:
             raise ValueError("merge > 0 needs refine >= 1 (got refine = %r)" % (refine,))
 
+    @staticmethod
+    def _check_split(split, merge):
+        """untangle()'s and calibrate_refined()'s `split`: hdg_refine_split's split sweeps in
+        the rounds that `merge` counts."""
+        if not isinstance(split, bool):
+            raise ValueError("split must be a bool (got %r)" % (split,))
+        if split and merge < 1:
+            raise ValueError("split needs merge >= 1, the rounds (got merge = %r)" % (merge,))
+
     # ------------------------------------------------------------------ untangle
     def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single", refine=0,
-                 merge=0):
+                 merge=0, split=False):
         """Untangle the commits of the test (or train) split with the trained classifier: per
         batch Engine.forward then Engine.untangle (hdg_untangle), so only each commit's hunk
         group ids and its integer row (include/hdgnn.h, HDG_UT_*) come to the host, never the
@@ -629,7 +638,11 @@ class graph2graph(object):
         merge > 0 (needs refine >= 1): the refinement is Engine.refine_merge (hdg_refine_merge:
         at most `merge` rounds of node sweeps and one group sweep, `refine` the total of node
         sweeps); the objective rows have 8 columns, the first four with their meaning
-        (HDG_RM_Q_*), and one more line reports rounds, merges and the objective."""
+        (HDG_RM_Q_*), and one more line reports rounds, merges and the objective.
+        split (needs merge >= 1): the refinement is Engine.refine_split with kinds "both"
+        (hdg_refine_split: every round also runs a split sweep, in which a group is cut in
+        two); the objective rows keep 8 columns, the last the accepted splits, and one more
+        line reports them."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
@@ -640,6 +653,7 @@ class graph2graph(object):
             raise ValueError("refine must be an int in [0, %d] (got %r)"
                              % (_lib.RF_MAX_SWEEPS, refine))
         self._check_merge(merge, refine)
+        self._check_split(split, merge)
         qslots = _lib.RM_Q_SLOTS if merge else _lib.RF_Q_SLOTS
         _, _, train, test, maps = self._compact()
         if self.load(self.checkpoint_dir):
@@ -655,7 +669,11 @@ class graph2graph(object):
             else:
                 m, lv, cv, _, lk = eng.agglomerate(db, rule=rule, method=method)
                 g, ut = eng.cut(m, lv, cv, lk, threshold=threshold, rule=rule)
-            if merge:
+            if split:
+                g, ut, rq = eng.refine_split(db, g, threshold=threshold, rule=rule,
+                                             max_sweeps=refine, max_rounds=merge, kinds="both")
+                qs.append(rq)
+            elif merge:
                 g, ut, rq = eng.refine_merge(db, g, threshold=threshold, rule=rule,
                                              max_sweeps=refine, max_rounds=merge)
                 qs.append(rq)
@@ -705,6 +723,10 @@ class graph2graph(object):
                       % (merge, int(qrows[:, _lib.RM_Q_ROUNDS].sum()),
                          int(qrows[:, _lib.RM_Q_MERGES].sum()),
                          int(qrows[:, _lib.RM_Q_NODE].sum()), int(qrows[:, _lib.RF_Q_END].sum())))
+            if split:
+                print('untangle split: %d splits in %d of %d commits'
+                      % (int(qrows[:, _lib.RS_Q_SPLITS].sum()),
+                         int(np.count_nonzero(qrows[:, _lib.RS_Q_SPLITS])), len(qrows)))
             for name in ("rand", "precision", "recall", "f1"):
                 print('untangle %s: %s (per-commit mean %s)' % (name, scores[name],
                                                                 scores[name + "_mean"]))
@@ -778,7 +800,7 @@ class graph2graph(object):
 
     # ------------------------------------------------------------------ calibrate_refined
     def calibrate_refined(self, args, part="train", rule="mean", score="f1", method="single",
-                          refine=8, ladder=(0.05, 0.95, 19), merge=0):
+                          refine=8, ladder=(0.05, 0.95, 19), merge=0, split=False):
         """The link threshold untangle(refine=N) should use: the rung of `ladder` = (lo, hi, n)
         (metrics.ladder) with the best pooled `score` of the REFINED groups over the commits of
         the train (or test) split -- the objective's threshold is not the tree's best cut,
@@ -796,7 +818,11 @@ class graph2graph(object):
         merge > 0: the threshold untangle(refine=N, merge=R) should use -- the ladder is
         Engine.refine_merge_ladder (hdg_refine_merge_ladder), every rung refined in at most
         `merge` rounds; rq has 8 columns, the first four with their meaning, and each rung's
-        line is followed by one with its rounds, merges and objective."""
+        line is followed by one with its rounds, merges and objective.
+        split (needs merge >= 1): the threshold untangle(refine=N, merge=R, split=True) should
+        use -- the ladder is Engine.refine_split_ladder with kinds "both"
+        (hdg_refine_split_ladder); rq keeps 8 columns, the last the accepted splits, and each
+        rung gets one more line with them."""
         import torch
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
@@ -807,6 +833,7 @@ class graph2graph(object):
             raise ValueError("refine must be an int in [1, %d] (got %r)"
                              % (_lib.RF_MAX_SWEEPS, refine))
         self._check_merge(merge, refine)
+        self._check_split(split, merge)
         qslots = _lib.RM_Q_SLOTS if merge else _lib.RF_Q_SLOTS
         thresholds = metrics.ladder(*ladder)
         T = len(thresholds)
@@ -821,7 +848,11 @@ class graph2graph(object):
             eng.forward(db)
             m, lv, cv, _, lk = (eng.linkage(db, rule=rule) if method == "single"
                                 else eng.agglomerate(db, rule=rule, method=method))
-            if merge:
+            if split:
+                ut, rq, _ = eng.refine_split_ladder(db, thresholds.tolist(), tree=(m, lv),
+                                                    rule=rule, max_sweeps=refine,
+                                                    max_rounds=merge, kinds="both")
+            elif merge:
                 ut, rq, _ = eng.refine_merge_ladder(db, thresholds.tolist(), tree=(m, lv),
                                                     rule=rule, max_sweeps=refine,
                                                     max_rounds=merge)
@@ -871,6 +902,10 @@ class graph2graph(object):
                              int(qrows[j, :, _lib.RM_Q_MERGES].sum()),
                              int(qrows[j, :, _lib.RM_Q_NODE].sum()),
                              int(qrows[j, :, _lib.RF_Q_END].sum())))
+                if split:
+                    print('calibrate refined rung %d split: %d splits in %d of %d commits'
+                          % (j, int(qrows[j, :, _lib.RS_Q_SPLITS].sum()),
+                             int(np.count_nonzero(qrows[j, :, _lib.RS_Q_SPLITS])), n))
             print('calibrate refined threshold: %r (rung %d), %s = %s' % (threshold, k, score, best))
             print('calibrate refined tree alone: threshold %r, %s = %s' % (tree_thr, score,
                                                                           tree_best))

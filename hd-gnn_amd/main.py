@@ -26,6 +26,9 @@ MI355X instead of a TF1 session.
     python hd-gnn_amd/main.py --Type untangle --link-threshold refined --link-refine 8 \\
         --link-merge 4                         # ... whole groups may merge between the sweeps:
                                                # up to 4 rounds of node sweeps + one group sweep
+    python hd-gnn_amd/main.py --Type untangle --link-threshold refined --link-refine 8 \\
+        --link-merge 4 --link-split            # ... and a fused group may be cut in two: every
+                                               # round also runs one split sweep
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -87,7 +90,10 @@ def _variant(argv):
     --link-merge R (default 0: none; at most 16; needs --link-refine N >= 1): the refinement
     runs in at most R rounds, each the node sweeps followed by one group sweep in which whole
     groups merge, N the total of node sweeps (hdg_refine_merge, hdg_refine_merge_ladder), in
-    --Type untangle and in the ladder of --link-threshold refined alike."""
+    --Type untangle and in the ladder of --link-threshold refined alike;
+    --link-split (needs --link-merge R >= 1): every round also runs one split sweep, in which a
+    group is cut in two from two seeds if that raises the objective (hdg_refine_split,
+    hdg_refine_split_ladder)."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
@@ -98,6 +104,7 @@ def _variant(argv):
     p.add_argument('--link-refine', type=int, default=0)
     p.add_argument('--link-ladder', type=_ladder, default=(0.05, 0.95, 19))
     p.add_argument('--link-merge', type=int, default=0)
+    p.add_argument('--link-split', action='store_true')
     a, rest = p.parse_known_args(argv)
     if a.link_threshold == 'refined' and a.link_refine < 1:
         p.error("--link-threshold refined needs --link-refine N with N >= 1")
@@ -105,6 +112,8 @@ def _variant(argv):
         p.error("--link-merge R needs 0 <= R <= 16")
     if a.link_merge and a.link_refine < 1:
         p.error("--link-merge needs --link-refine N with N >= 1")
+    if a.link_split and a.link_merge < 1:
+        p.error("--link-split needs --link-merge R with R >= 1")
     return a, rest
 
 
@@ -182,6 +191,8 @@ def main(argv=None, model_cls=None):
                        ladder=extra.link_ladder, **how)
         # rounds with group sweeps only when asked for: without the flag every call is as it was
         rounds = {'merge': extra.link_merge} if extra.link_merge else {}
+        if extra.link_split:         # split sweeps in those rounds, only when asked for
+            rounds['split'] = True
         refined.update(rounds)
         if args.Type == 'untangle':  # not in the reference: hunk groups per commit, on the device
             threshold = extra.link_threshold

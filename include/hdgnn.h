@@ -20,8 +20,8 @@
  *   - every pointer is a caller-owned DEVICE pointer (the library never allocates);
  *     `stream` is a hipStream_t passed as void*; all work is enqueued on it, no host
  *     synchronisation happens inside any call (graph-capturable).  The one exception:
- *     hdg_refine_ladder's and hdg_refine_merge_ladder's `thresholds` is a HOST array, read
- *     during the call only.
+ *     `thresholds` of hdg_refine_ladder, hdg_refine_merge_ladder and
+ *     hdg_refine_split_ladder is a HOST array, read during the call only.
  *   - return 0 on success, HDG_EINVAL for a shape/argument error, or the hipError_t
  *     of a failed launch; hdg_last_error() gives a thread-local message.
  *   - parameters are one flat fp32 vector in tf.global_variables() order with TF
@@ -689,6 +689,92 @@ int    hdg_refine_merge_ladder(const hdg_shape* shape, const hdg_batch* batch,
                                int32_t* groups  /* [n_rungs][batch][nc] or NULL */,
                                uint64_t* ut     /* [n_rungs][batch][HDG_RF_SLOTS] */,
                                int64_t* rq      /* [n_rungs][batch][HDG_RM_Q_SLOTS] */,
+                               void* workspace, void* stream);
+
+/* hdg_refine_split, hdg_refine_split_ladder: the rounds of hdg_refine_merge with a third move,
+ * the SPLIT of one group in two.  Single linkage, or a tree cut below the right threshold,
+ * fuses two tight groups through one wrong high score; a hunk of such a group keeps a positive
+ * sum towards it (its own half outweighs the other), so it never leaves for the empty slot,
+ * group sweeps only merge, and the search reports "converged" although cutting the group would
+ * raise Q by the negative sum between the halves.  A SPLIT SWEEP bisects a slot from two seeds
+ * (hdgnn.metrics.refine_split and refine_split_ladder restate the calls, integer for integer).
+ * Everything not restated here is hdg_refine's and hdg_refine_merge's, above: weights, pairs
+ * that are no edge, a_pq, t', the start and the slots, the node sweep, the group sweep, the
+ * dense output ids and the ut row (HDG_RF_MOVES counts node moves only).
+ *
+ *   kinds    HDG_RS_MERGE, HDG_RS_SPLIT or both: the sweeps a round runs after its node phase
+ *   rounds   repeat: (1) the node phase, as hdg_refine_merge's; (2) with HDG_RS_MERGE one group
+ *            sweep; (3) with HDG_RS_SPLIT one split sweep; (4) stop if this round merged nothing
+ *            and split nothing, or max_rounds rounds have run, or the total of node sweeps has
+ *            reached max_sweeps.  Every move, merge and split raises Q by at least 1
+ *   split sweep  visits the slots g = 0, 1, .., nc-1 in that order, each visit seeing the splits
+ *            of the earlier visits.  A slot is skipped if it holds fewer than 2 hunks when its
+ *            turn comes, or if it received its members by a split of this same sweep (so every
+ *            hunk is in at most one attempt per sweep).  Otherwise, with e the smallest empty
+ *            slot (one exists whenever a slot holds 2 hunks):
+ *            seeds: the pair (s1, s2), s1 < s2, both in g, with the smallest a_pq; among equals
+ *              the lowest p, then the lowest q.  If that gain is >= 0 the visit ends and
+ *              nothing changes (every cut of g sums non-negative gains)
+ *            assignment pass: side G = {s1}, side E = {s2}; the other members of g take their
+ *              turns in index order; for member m, T_G = the sum of a_mx over x already on side
+ *              G and T_E likewise (members not yet assigned do not count); m joins E iff
+ *              T_E > T_G strictly, else G
+ *            correction passes: at most HDG_RS_PASSES - 1.  A pass visits the members other than
+ *              the two seeds in index order, each seeing the earlier moves; m on side X changes
+ *              side iff the sum over the other side is strictly above the sum over X \ {m}.  A
+ *              pass without a change ends them
+ *            decision: C = the sum of a_xy over x in G, y in E (int64).  If C < 0 the members of
+ *              E take slot e, G keeps slot g, Q rises by -C, the split counts and e is marked
+ *              as filled by this sweep; otherwise nothing changes
+ *   bounds   every side sum is an int32 (at most 2047 partners of magnitude 2^19); |C| <= 2^39
+ *            as a merge gain; the seed key holds the gain biased into 21 bits and two 11-bit
+ *            indices
+ *   rq       rows of HDG_RS_Q_SLOTS i64: slots 0 .. 6 as hdg_refine_merge's, CONVERGED being
+ *            1 iff the last node phase ended on a sweep without a move and the last round
+ *            merged nothing and split nothing; HDG_RS_Q_SPLITS counts the accepted splits
+ * Consequences: (A) with kinds = HDG_RS_MERGE, groups, ut and rq equal hdg_refine_merge's
+ * integer for integer (slot 7 is 0 in both); (B) HDG_RM_Q_NODE equals hdg_refine's
+ * HDG_RF_Q_END at the same max_sweeps under every kinds; (C) Q_END - Q_NODE >= MERGES + SPLITS;
+ * (D) Q_END equals Q recomputed from the returned groups.
+ * hdg_refine_split_ladder: rung k holds what hdg_cut(merges, levels, thresholds[k], rule)
+ * followed by hdg_refine_split(thresholds[k], .., groups_in = those groups) writes -- or the
+ * singleton start without a tree, as hdg_refine_merge_ladder; thresholds is a HOST array.
+ * Argument types, array shapes and workspaces are hdg_refine_merge's and
+ * hdg_refine_merge_ladder's.  Two launches each: the weights kernel, unchanged, and the sweep
+ * block with the chosen sweeps (k_rs_sweep, k_rsl_sweep), one 1024-thread block per commit
+ * (per rung and commit).  A split visit compacts the slot's members in index order in LDS,
+ * finds the seeds in one walk over the members' rows, and makes one step per member and pass:
+ * the member's row read one member ahead, the two side sums by a wave reduction and one int32
+ * LDS atomic per wave and side, one barrier, the same decision in every thread; C is carried
+ * along.  The visits are bounded by nc, the passes by HDG_RS_PASSES, a pass's steps by the
+ * slot's size.  No host synchronisation, no block waits for another, no float atomics, no
+ * allocation: graph-capturable, the same bits on every run.  HDG_EINVAL (the message starts
+ * "hdg_refine_split:" or "hdg_refine_split_ladder:"; nothing is launched) for everything the
+ * merge calls reject, kinds outside {1, 2, 3}, or any flag bit.                            */
+#define HDG_RS_MERGE 1         /* kinds bit: a round runs hdg_refine_merge's group sweep   */
+#define HDG_RS_SPLIT 2         /* kinds bit: a round runs a split sweep                    */
+#define HDG_RS_PASSES 4        /* passes of one split attempt: 1 assignment + 3 correction */
+#define HDG_RS_Q_SLOTS 8       /* = HDG_RM_Q_SLOTS; slots 0 .. 6 as HDG_RM_Q_*             */
+#define HDG_RS_Q_SPLITS 7      /* splits accepted                                          */
+
+int    hdg_refine_split(const hdg_shape* shape, const hdg_batch* batch, const float* probs,
+                        float threshold, int32_t rule, int32_t max_sweeps, int32_t max_rounds,
+                        int32_t kinds, int32_t flags,
+                        const int32_t* groups_in /* [batch][nc] or NULL */,
+                        int32_t* groups          /* [batch][nc] */,
+                        uint64_t* ut             /* [batch][HDG_RF_SLOTS] */,
+                        int64_t* rq              /* [batch][HDG_RS_Q_SLOTS] */,
+                        void* workspace, void* stream);
+int    hdg_refine_split_ladder(const hdg_shape* shape, const hdg_batch* batch,
+                               const float* probs,
+                               const float* thresholds /* HOST, [n_rungs] */, int32_t n_rungs,
+                               int32_t rule, int32_t max_sweeps, int32_t max_rounds,
+                               int32_t kinds, int32_t flags,
+                               const int32_t* merges /* [batch][nc-1][2] or NULL */,
+                               const float* levels   /* [batch][nc-1]    or NULL */,
+                               int32_t* groups  /* [n_rungs][batch][nc] or NULL */,
+                               uint64_t* ut     /* [n_rungs][batch][HDG_RF_SLOTS] */,
+                               int64_t* rq      /* [n_rungs][batch][HDG_RS_Q_SLOTS] */,
                                void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
