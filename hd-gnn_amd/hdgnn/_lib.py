@@ -96,6 +96,10 @@ RS_MERGE, RS_SPLIT = 1, 2
 RS_KINDS = {"merge": RS_MERGE, "split": RS_SPLIT, "both": RS_MERGE | RS_SPLIT}
 RS_PASSES = 4
 RS_Q_SLOTS, RS_Q_SPLITS = 8, 7
+# hdg_match's row per set and commit (include/hdgnn.h): mt[S][B][MT_SLOTS] u64, slot 7 is 0
+MT_SLOTS = 8
+MT_GROUPS, MT_TGROUPS, MT_MATCHED, MT_PURITY, MT_COVER, MT_CELLS, MT_ISOLATED = range(7)
+MT_MAX_SETS = 64
 
 
 def untangle_blocks(nc):
@@ -126,7 +130,8 @@ EXPORTS = ["hdg_version", "hdg_last_error", "hdg_resolve_path", "hdg_param_count
            "hdg_refine_workspace_bytes", "hdg_refine",
            "hdg_refine_ladder_workspace_bytes", "hdg_refine_ladder",
            "hdg_refine_merge", "hdg_refine_merge_ladder",
-           "hdg_refine_split", "hdg_refine_split_ladder"]
+           "hdg_refine_split", "hdg_refine_split_ladder",
+           "hdg_match_workspace_bytes", "hdg_match"]
 
 _lib = None
 
@@ -192,6 +197,9 @@ def load(path=None):
                                      vp, vp, vp, vp]
     lib.hdg_refine_split_ladder.argtypes = [P(Shape), P(Batch), vp, P(f32), i32, i32, i32, i32,
                                             i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.hdg_match_workspace_bytes.argtypes = [P(Shape), i32]
+    lib.hdg_match_workspace_bytes.restype = ctypes.c_size_t
+    lib.hdg_match.argtypes = [P(Shape), P(Batch), vp, i32, vp, vp, vp, vp, vp]
     lib.hdg_dp_mailbox_bytes.restype = ctypes.c_size_t
     lib.hdg_dp_mailbox_alloc.argtypes = [P(vp), vp]
     lib.hdg_dp_mailbox_open.argtypes = [vp, P(vp)]

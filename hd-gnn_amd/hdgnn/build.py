@@ -14,7 +14,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 # every translation unit of libhdgnn.so, in csrc/ (the one list: the hazard scan and the
 # host-sanitizer build of the tests take theirs from here)
-SOURCES = ("hdgnn.hip", "wide.hip", "eval.hip", "untangle.hip", "linkage.hip", "agglo.hip", "refine.hip", "dp.hip", "prep.hip", "ckpt.cpp")
+SOURCES = ("hdgnn.hip", "wide.hip", "eval.hip", "untangle.hip", "linkage.hip", "agglo.hip", "refine.hip", "match.hip", "dp.hip", "prep.hip", "ckpt.cpp")
 
 
 def device_sources():

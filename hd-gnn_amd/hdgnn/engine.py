@@ -704,3 +704,47 @@ class Engine:
             ctypes.c_void_p(ut.data_ptr()), ctypes.c_void_p(rq.data_ptr()),
             ctypes.c_void_p(ws.data_ptr()), self._stream()))
         return ut, rq, out
+
+    def _match_args(self, groups, mate):
+        """match()'s `groups` and `mate`, checked as _refine() checks its groups -> the ids as
+        [S][B][nc] (a view) and S."""
+        if not isinstance(mate, bool):
+            raise ValueError("mate must be a bool (got %r)" % (mate,))
+        ok = (isinstance(groups, torch.Tensor) and groups.device == self.device
+              and groups.dtype == torch.int32 and groups.is_contiguous())
+        if ok and groups.dim() == 2:
+            groups = groups.unsqueeze(0)
+        if not (ok and groups.dim() == 3 and tuple(groups.shape[1:]) == (self.batch, self.nc)
+                and 1 <= groups.shape[0] <= _lib.MT_MAX_SETS):
+            raise ValueError("groups must be a contiguous int32 [%d][%d] or [S][%d][%d] tensor on "
+                             "%s, 1 <= S <= %d" % (self.batch, self.nc, self.batch, self.nc,
+                                                   self.device, _lib.MT_MAX_SETS))
+        return groups, int(groups.shape[0])
+
+    def match(self, dbatch, groups, mate=False):
+        """hdg_match: how many hunks are in the right group -- per set of `groups` (int32
+        [B][nc] or [S][B][nc] on this device, 1 <= S <= MT_MAX_SETS: what untangle(), cut(), a
+        refine call or a ladder with groups=True returned; equal ids in [0, nc) are together,
+        any other id is alone) and commit the best one-to-one assignment of predicted to true
+        groups (include/hdgnn.h) -> (mt int64 [S][B][MT_SLOTS], mate int32 [S][B][nc] or None
+        unless `mate`, tgroups int32 [B][nc]) as fresh device tensors
+        (hdgnn.metrics.scores_from_match turns mt into scores, best_rung_match picks a ladder's
+        rung).  Enqueued on the current stream; nothing is copied to the host.  The workspace is
+        allocated on the first call and kept."""
+        groups, S = self._match_args(groups, mate)
+        self._check(dbatch)
+        ws = self._workspace("_mt_workspace", lambda: self.lib.hdg_match_workspace_bytes(
+            ctypes.byref(self.shape), _lib.MT_MAX_SETS), torch.int64)
+        # u64 counts, every value < 2^63: int64 reads them as they are
+        mt = torch.empty(S, self.batch, _lib.MT_SLOTS, dtype=torch.int64, device=self.device)
+        out = (torch.empty(S, self.batch, self.nc, dtype=torch.int32, device=self.device)
+               if mate else None)
+        tgroups = torch.empty(self.batch, self.nc, dtype=torch.int32, device=self.device)
+        b = dbatch.struct()
+        _lib.check(self.lib.hdg_match(ctypes.byref(self.shape), ctypes.byref(b),
+                                      ctypes.c_void_p(groups.data_ptr()), S,
+                                      None if out is None else ctypes.c_void_p(out.data_ptr()),
+                                      ctypes.c_void_p(tgroups.data_ptr()),
+                                      ctypes.c_void_p(mt.data_ptr()),
+                                      ctypes.c_void_p(ws.data_ptr()), self._stream()))
+        return mt, out, tgroups

@@ -945,3 +945,182 @@ def best_rung(ut_ladder, thresholds, score="f1"):
     good = ~np.isnan(vals)
     i = int(np.flatnonzero(good & (vals == vals[good].max()))[0]) if good.any() else 0
     return i, float(thr[i]), float(vals[i]), vals
+
+
+# ---------------------------------------------------------------------------------------
+# Matching: how many hunks are in the right group under the best one-to-one assignment of
+# predicted to true groups, as hdg_match computes it on the device (include/hdgnn.h,
+# HDG_MT_*), its host restatement with an integer assignment solver, the scores that follow
+# and the rung of a ladder with the best pooled accuracy.
+# ---------------------------------------------------------------------------------------
+MT_SLOTS = 8
+MT_GROUPS, MT_TGROUPS, MT_MATCHED, MT_PURITY, MT_COVER, MT_CELLS, MT_ISOLATED = range(7)
+MT_MAX_SETS = 64
+
+
+def assign_max(table):
+    """Integer table (K, M) of non-negative weights -> (value, col int64 (K,)): the largest
+    sum of table[i, col[i]] over one-to-one assignments that assign the smaller side fully
+    (col[i] = -1 for a row left out when K > M), an empty cell counting 0.  Shortest
+    augmenting paths with integer potentials on the negated table (Kuhn-Munkres in
+    Jonker-Volgenant's form), rows on the smaller side, every scan a numpy operation over the
+    columns, ties between equal slacks to the lowest column.  The value is unique, the
+    assignment one optimum."""
+    a = np.asarray(table)
+    if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("table must be a 2-d integer array (got %r, %s)" % (a.shape, a.dtype))
+    if a.size and a.min() < 0:
+        raise ValueError("table must be non-negative")
+    K, M = a.shape
+    if K > M:
+        value, row = assign_max(a.T)
+        col = np.full(K, -1, np.int64)
+        col[row] = np.arange(M)
+        return value, col
+    cost = -a.astype(np.int64)
+    inf = np.int64(1) << 60
+    u, v = np.zeros(K, np.int64), np.zeros(M, np.int64)
+    pcol = np.full(M, -1, np.int64)               # the row assigned to a column
+    for i in range(K):
+        minv = np.full(M, inf, np.int64)
+        way = np.full(M, -1, np.int64)
+        used = np.zeros(M, bool)
+        i0, j0 = i, -1
+        while True:
+            cur = cost[i0] - u[i0] - v
+            better = ~used & (cur < minv)
+            minv[better] = cur[better]
+            way[better] = j0
+            j1 = int(np.argmin(np.where(used, inf, minv)))      # the first of equals
+            delta = minv[j1]
+            u[pcol[used]] += delta
+            u[i] += delta
+            v[used] -= delta
+            minv[~used] -= delta
+            used[j1] = True
+            j0 = j1
+            if pcol[j1] < 0:
+                break
+            i0 = pcol[j1]
+        while j0 >= 0:
+            j1 = way[j0]
+            pcol[j0] = i if j1 < 0 else pcol[j1]
+            j0 = j1
+    col = np.full(K, -1, np.int64)
+    hit = pcol >= 0
+    col[pcol[hit]] = np.flatnonzero(hit)
+    return int(a[np.arange(K), col].sum()) if K else 0, col
+
+
+def _match_one(g, t):
+    """Predicted ids g (by smallest member) and dense true ids t of one commit -> (mt row,
+    mate): the table with np.add.at, the isolated cells taken as they are, assign_max on the
+    residual graph."""
+    nc = len(g)
+    gd = (np.cumsum(g == np.arange(nc)) - 1)[g]                 # dense, by smallest member
+    G, TG = int(gd.max()) + 1, int(t.max()) + 1
+    keys, first, w = np.unique(gd.astype(np.int64) * TG + t, return_index=True,
+                               return_counts=True)
+    cg, ct = keys // TG, keys % TG                                # the non-zero cells
+    rmax, cmax = np.zeros(G, np.int64), np.zeros(TG, np.int64)
+    np.maximum.at(rmax, cg, w)
+    np.maximum.at(cmax, ct, w)
+    rdeg, cdeg = np.bincount(cg, minlength=G), np.bincount(ct, minlength=TG)
+    iso = (rdeg[cg] == 1) & (cdeg[ct] == 1)
+    gm = np.full(G, -1, np.int64)
+    gm[cg[iso]] = ct[iso]
+    matched = int(w[iso].sum())
+    if not iso.all():
+        rows, ri = np.unique(cg[~iso], return_inverse=True)
+        cols, ci = np.unique(ct[~iso], return_inverse=True)
+        table = np.zeros((len(rows), len(cols)), np.int64)
+        np.add.at(table, (ri, ci), w[~iso])
+        value, col = assign_max(table)
+        matched += value
+        hit = col >= 0
+        hit[hit] = table[np.flatnonzero(hit), col[hit]] > 0       # not through an empty cell
+        gm[rows[hit]] = cols[col[hit]]
+    row = (G, TG, matched, int(rmax.sum()), int(cmax.sum()), len(keys), int(iso.sum()), 0)
+    return row, gm[gd].astype(np.int32)
+
+
+def match_counts(label_onehot, groups):
+    """(B, 2, R) one-hot labels, R = Nc (Nc - 1), and group ids int (S, B, Nc) or (B, Nc) ->
+    (mt int64 (S, B, MT_SLOTS), mate int32 (S, B, Nc), tgroups int32 (B, Nc)): the host
+    restatement of hdg_match, definitions as in include/hdgnn.h.  Predicted groups by
+    refine()'s start rule (equal ids in [0, Nc) together, any other id alone), true groups
+    untangle_counts()'s.  mate is one optimal assignment: under ties the device may return
+    another; both satisfy #{p : mate[p] == tgroups[p]} == MATCHED."""
+    from .data import pair_index
+    label = np.asarray(label_onehot)
+    B, R = label.shape[0], label.shape[2]
+    nc = _nc_of(R)
+    groups = np.asarray(groups)
+    if groups.ndim == 2:
+        groups = groups[None]
+    if groups.ndim != 3 or groups.shape[1:] != (B, nc) or not 1 <= len(groups) <= MT_MAX_SETS:
+        raise ValueError("groups must be (S, %d, %d) or (%d, %d) with 1 <= S <= %d (got %r)"
+                         % (B, nc, B, nc, MT_MAX_SETS, groups.shape))
+    groups = groups.astype(np.int64)
+    S = len(groups)
+    I, J = pair_index(nc)
+    iu, ju = np.triu_indices(nc, 1)
+    Y = np.zeros((nc, nc), bool)
+    every = np.arange(nc)
+    mt = np.zeros((S, B, MT_SLOTS), np.int64)
+    mate = np.zeros((S, B, nc), np.int32)
+    tgroups = np.zeros((B, nc), np.int32)
+    for b in range(B):
+        Y[I, J] = label[b, 1] > label[b, 0]
+        ylink = Y[iu, ju] | Y[ju, iu]
+        tgroups[b] = _components(nc, iu[ylink], ju[ylink])
+        for s in range(S):
+            ids = groups[s, b]
+            ok = (ids >= 0) & (ids < nc)
+            low = np.full(nc, nc, np.int64)
+            np.minimum.at(low, ids[ok], every[ok])
+            g = every.copy()
+            g[ok] = low[ids[ok]]
+            mt[s, b], mate[s, b] = _match_one(g, tgroups[b].astype(np.int64))
+    return mt, mate, tgroups
+
+
+def scores_from_match(mt, nc):
+    """(n_commits, MT_SLOTS) integer table and nc, the hunks per commit (the length of the
+    group ids) -> dict.  accuracy: matched hunks pooled over all commits, sum MATCHED /
+    (n_commits nc); accuracy_mean: the mean of the per-commit MATCHED / nc (equal to the
+    pooled value, every commit having nc hunks; kept beside it as the other score dicts keep
+    theirs); purity, cover: pooled likewise; exact: share of commits with MATCHED == nc (the
+    predicted partition is the true one); groups_mean, tgroups_mean.  Without commits every
+    value is nan (_ratio's rule)."""
+    mt = np.asarray(mt).reshape(-1, MT_SLOTS).astype(np.int64)
+    nc = int(nc)
+    if nc < 1:
+        raise ValueError("nc must be positive (got %r)" % (nc,))
+    n = len(mt)
+    out = {"accuracy": float(_ratio(mt[:, MT_MATCHED].sum(), n * nc)),
+           "accuracy_mean": _nanmean(_ratio(mt[:, MT_MATCHED], np.full(n, nc))),
+           "purity": float(_ratio(mt[:, MT_PURITY].sum(), n * nc)),
+           "cover": float(_ratio(mt[:, MT_COVER].sum(), n * nc))}
+    nan = float("nan")
+    out["exact"] = float((mt[:, MT_MATCHED] == nc).mean()) if n else nan
+    out["groups_mean"] = float(mt[:, MT_GROUPS].mean()) if n else nan
+    out["tgroups_mean"] = float(mt[:, MT_TGROUPS].mean()) if n else nan
+    return out
+
+
+def best_rung_match(mt_ladder, thresholds, nc):
+    """mt_ladder int (T, n_commits, MT_SLOTS), the T thresholds and nc -> (index, threshold,
+    accuracy, per-rung accuracies float64 (T,)): best_rung's contract on the pooled accuracy
+    of scores_from_match.  A nan score never wins; ties go to the lowest index; if every
+    score is nan: index 0, with a nan score."""
+    thr = _rungs(thresholds)
+    mt = np.asarray(mt_ladder)
+    if mt.ndim != 3 or mt.shape[0] != len(thr) or mt.shape[-1] != MT_SLOTS:
+        raise ValueError("mt_ladder must be (%d, n_commits, %d) (got %r)"
+                         % (len(thr), MT_SLOTS, mt.shape))
+    vals = np.array([scores_from_match(mt[k], nc)["accuracy"] for k in range(len(thr))],
+                    np.float64)
+    good = ~np.isnan(vals)
+    i = int(np.flatnonzero(good & (vals == vals[good].max()))[0]) if good.any() else 0
+    return i, float(thr[i]), float(vals[i]), vals

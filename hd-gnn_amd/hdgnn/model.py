@@ -618,7 +618,7 @@ class graph2graph(object):
 
     # ------------------------------------------------------------------ untangle
     def untangle(self, args, part="test", threshold=0.5, rule="mean", method="single", refine=0,
-                 merge=0, split=False):
+                 merge=0, split=False, match=False):
         """Untangle the commits of the test (or train) split with the trained classifier: per
         batch Engine.forward then Engine.untangle (hdg_untangle), so only each commit's hunk
         group ids and its integer row (include/hdgnn.h, HDG_UT_*) come to the host, never the
@@ -642,8 +642,15 @@ class graph2graph(object):
         split (needs merge >= 1): the refinement is Engine.refine_split with kinds "both"
         (hdg_refine_split: every round also runs a split sweep, in which a group is cut in
         two); the objective rows keep 8 columns, the last the accepted splits, and one more
-        line reports them."""
+        line reports them.
+        match: after the groups are final, whatever produced them, one Engine.match call per
+        batch (hdg_match: the hunks in the right group under the best one-to-one assignment of
+        predicted to true groups); one more line reports accuracy, its per-commit mean, purity
+        and cover (metrics.scores_from_match), match_counts<Ne>.npy holds each commit's row
+        (HDG_MT_*), and the scores dict gains "match", that dict."""
         import torch
+        if not isinstance(match, bool):
+            raise ValueError("match must be a bool (got %r)" % (match,))
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
         if method not in _lib.AG_METHODS:
@@ -661,7 +668,7 @@ class graph2graph(object):
         else:
             print(" [!] Load failed...")
         eng = self.engine
-        rows, ids, qs = [], [], []
+        rows, ids, qs, ms = [], [], [], []
         for db in self._device_batches(train if part == "train" else test, maps):
             eng.forward(db)
             if method == "single":
@@ -680,6 +687,8 @@ class graph2graph(object):
             elif refine:
                 g, ut, rq = eng.refine(db, g, threshold=threshold, rule=rule, max_sweeps=refine)
                 qs.append(rq)
+            if match:
+                ms.append(eng.match(db, g)[0][0])
             ids.append(g)
             rows.append(ut)
         nb, lb = len(rows), self.local_batch
@@ -699,9 +708,18 @@ class graph2graph(object):
                 qrows = self._gather(qrows).reshape(self.world, nb, lb, qslots)
                 qrows = qrows.transpose(1, 0, 2, 3)
             qrows = np.ascontiguousarray(qrows.reshape(-1, qslots)).astype(np.int64)
+        if match:
+            mrows = (torch.stack(ms).cpu().numpy() if nb
+                     else np.zeros((0, lb, _lib.MT_SLOTS), np.int64))
+            if self.world > 1 and nb:
+                mrows = self._gather(mrows).reshape(self.world, nb, lb, _lib.MT_SLOTS)
+                mrows = mrows.transpose(1, 0, 2, 3)
+            mrows = np.ascontiguousarray(mrows.reshape(-1, _lib.MT_SLOTS)).astype(np.int64)
         table = np.ascontiguousarray(table.reshape(-1, _lib.UT_SLOTS)).astype(np.int64)
         groups = np.ascontiguousarray(groups.reshape(-1, self.Nc)).astype(np.int32)
         scores = metrics.scores_from_untangle(table)
+        if match:
+            scores["match"] = metrics.scores_from_match(mrows, self.Nc)
         if self.rank == 0:
             step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
             os.makedirs(step_dir, exist_ok=True)
@@ -733,6 +751,11 @@ class graph2graph(object):
             print('untangle exact partitions: %s, group count match: %s (%d commits)'
                   % (scores["exact"], scores["group_count_match"], len(table)))
             print('untangle nan pairs: %d' % scores["nan_pairs"])
+            if match:
+                np.save(step_dir + 'match_counts' + str(self.Ne) + '.npy', mrows)
+                sm = scores["match"]
+                print('untangle match: accuracy %s (per-commit mean %s), purity %s, cover %s'
+                      % (sm["accuracy"], sm["accuracy_mean"], sm["purity"], sm["cover"]))
         return scores, table, groups
 
     # ------------------------------------------------------------------ calibrate
@@ -751,6 +774,9 @@ class graph2graph(object):
         (hdg_agglomerate) and the threshold is the one untangle(method=...) should use; the
         files are agglo_<method>_levels<Ne>.npy, _curve, _merges and _counts."""
         import torch
+        if score == "acc":
+            raise ValueError("score 'acc' needs a matching per cut: use calibrate_refined, which "
+                             "scores the rungs of a ladder with hdg_match")
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
         if method not in _lib.AG_METHODS:
@@ -822,8 +848,17 @@ class graph2graph(object):
         split (needs merge >= 1): the threshold untangle(refine=N, merge=R, split=True) should
         use -- the ladder is Engine.refine_split_ladder with kinds "both"
         (hdg_refine_split_ladder); rq keeps 8 columns, the last the accepted splits, and each
-        rung gets one more line with them."""
+        rung gets one more line with them.
+        score "acc": the rung is chosen by the pooled matching accuracy -- the hunks in the right
+        group under the best one-to-one assignment of predicted to true groups, over all hunks
+        (metrics.best_rung_match).  The ladder leaves its groups on the device and one
+        Engine.match call per batch (hdg_match) scores the T rungs there; the "tree alone" lines
+        compare with the tree's plain cuts at the same T thresholds (Engine.cut per rung,
+        stacked, one more Engine.match call), the exactly best cut over all Nc - 1 cuts not being
+        available for this score.  The scores dict gains "match" (metrics.scores_from_match of
+        the chosen rung) and refine_ladder_match<Ne>.npy holds the rows [T][n_commits][8]."""
         import torch
+        acc = score == "acc"
         if part not in ("train", "test"):
             raise ValueError("part must be 'train' or 'test' (got %r)" % (part,))
         if method not in _lib.AG_METHODS:
@@ -844,48 +879,67 @@ class graph2graph(object):
             print(" [!] Load failed...")
         eng = self.engine
         outs = []
+        more = {"groups": True} if acc else {}     # without "acc" every call is as it was
         for db in self._device_batches(train if part == "train" else test, maps):
             eng.forward(db)
             m, lv, cv, _, lk = (eng.linkage(db, rule=rule) if method == "single"
                                 else eng.agglomerate(db, rule=rule, method=method))
             if split:
-                ut, rq, _ = eng.refine_split_ladder(db, thresholds.tolist(), tree=(m, lv),
-                                                    rule=rule, max_sweeps=refine,
-                                                    max_rounds=merge, kinds="both")
+                ut, rq, lg = eng.refine_split_ladder(db, thresholds.tolist(), tree=(m, lv),
+                                                     rule=rule, max_sweeps=refine,
+                                                     max_rounds=merge, kinds="both", **more)
             elif merge:
-                ut, rq, _ = eng.refine_merge_ladder(db, thresholds.tolist(), tree=(m, lv),
-                                                    rule=rule, max_sweeps=refine,
-                                                    max_rounds=merge)
+                ut, rq, lg = eng.refine_merge_ladder(db, thresholds.tolist(), tree=(m, lv),
+                                                     rule=rule, max_sweeps=refine,
+                                                     max_rounds=merge, **more)
             else:
-                ut, rq, _ = eng.refine_ladder(db, thresholds.tolist(), tree=(m, lv), rule=rule,
-                                              max_sweeps=refine)
+                ut, rq, lg = eng.refine_ladder(db, thresholds.tolist(), tree=(m, lv), rule=rule,
+                                               max_sweeps=refine, **more)
             # batch-major like the tree's arrays, the rungs inside: [lb][T][slots]
             outs.append((lv, cv, lk, ut.transpose(0, 1).contiguous(),
                          rq.transpose(0, 1).contiguous()))
+            if acc:                    # the rungs' groups and the tree's plain cuts, matched
+                cuts = torch.stack([eng.cut(m, lv, cv, lk, threshold=float(t), rule=rule)[0]
+                                    for t in thresholds])
+                outs[-1] += (eng.match(db, lg)[0].transpose(0, 1).contiguous(),
+                             eng.match(db, cuts)[0].transpose(0, 1).contiguous())
         nb, lb, n1 = len(outs), self.local_batch, self.Nc - 1
         tails = ((n1,), (n1, 2), (_lib.LK_SLOTS,), (T, _lib.RF_SLOTS), (T, qslots))
         dtypes = (np.float32, np.int32, np.int64, np.int64, np.int64)
+        if acc:
+            tails += ((T, _lib.MT_SLOTS),) * 2
+            dtypes += (np.int64,) * 2
         arrs = [(torch.stack([o[i] for o in outs]).cpu().numpy() if nb
-                 else np.zeros((0, lb) + tails[i], dtypes[i])) for i in range(5)]
+                 else np.zeros((0, lb) + tails[i], dtypes[i])) for i in range(len(tails))]
         eng.check_status()
         if self.world > 1 and nb:      # rank-major (W nb, lb, ..) -> batch-major commit order
             arrs = [self._gather(a).reshape((self.world, nb, lb) + tails[i])
                     .transpose((1, 0, 2) + tuple(range(3, 3 + len(tails[i]))))
                     for i, a in enumerate(arrs)]
         levels, curve, lk, table, qrows = (np.ascontiguousarray(a.reshape((-1,) + tails[i]))
-                                           for i, a in enumerate(arrs))
+                                           for i, a in enumerate(arrs[:5]))
         curve, lk = curve.astype(np.int64), lk.astype(np.int64)
         table = np.ascontiguousarray(table.transpose(1, 0, 2)).astype(np.int64)    # [T][n][8]
         qrows = np.ascontiguousarray(qrows.transpose(1, 0, 2)).astype(np.int64)
-        k, threshold, best, vals = metrics.best_rung(table, thresholds, score)
-        scores = metrics.scores_from_untangle(table[k])
-        tree_thr, tree_best, _ = metrics.best_threshold(levels, curve, lk, rule, score)
+        if acc:
+            mrows, trows = (np.ascontiguousarray(a.reshape((-1,) + tails[5]).transpose(1, 0, 2))
+                            .astype(np.int64) for a in arrs[5:])
+            k, threshold, best, vals = metrics.best_rung_match(mrows, thresholds, self.Nc)
+            scores = metrics.scores_from_untangle(table[k])
+            scores["match"] = metrics.scores_from_match(mrows[k], self.Nc)
+            _, tree_thr, tree_best, _ = metrics.best_rung_match(trows, thresholds, self.Nc)
+        else:
+            k, threshold, best, vals = metrics.best_rung(table, thresholds, score)
+            scores = metrics.scores_from_untangle(table[k])
+            tree_thr, tree_best, _ = metrics.best_threshold(levels, curve, lk, rule, score)
         if self.rank == 0:
             step_dir = 'outputSelf/%s/model_%d/%s/' % (args.Repo, self.variant, self.Step)
             os.makedirs(step_dir, exist_ok=True)
             np.save(step_dir + 'refine_ladder_thresholds' + str(self.Ne) + '.npy', thresholds)
             np.save(step_dir + 'refine_ladder_counts' + str(self.Ne) + '.npy', table)
             np.save(step_dir + 'refine_ladder_objective' + str(self.Ne) + '.npy', qrows)
+            if acc:
+                np.save(step_dir + 'refine_ladder_match' + str(self.Ne) + '.npy', mrows)
             n = table.shape[1]
             print('calibrate refined rule: %s, part %s (%d commits), method %s, %d sweeps at most'
                   % (rule, part, n, method, refine))

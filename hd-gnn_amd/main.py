@@ -29,6 +29,11 @@ MI355X instead of a TF1 session.
     python hd-gnn_amd/main.py --Type untangle --link-threshold refined --link-refine 8 \\
         --link-merge 4 --link-split            # ... and a fused group may be cut in two: every
                                                # round also runs one split sweep
+    python hd-gnn_amd/main.py --Type untangle --link-match
+                                               # ... and how many hunks are in the right group
+                                               # (best assignment of predicted to true groups)
+    python hd-gnn_amd/main.py --Type untangle --link-threshold refined --link-refine 8 \\
+        --link-score acc --link-match          # the ladder's rung chosen by that accuracy
 
 The dataset loader is the reference's utils2.read_data (put its directory on
 PYTHONPATH, as the reference's own main.py expects it next to itself).
@@ -93,19 +98,26 @@ def _variant(argv):
     --Type untangle and in the ladder of --link-threshold refined alike;
     --link-split (needs --link-merge R >= 1): every round also runs one split sweep, in which a
     group is cut in two from two seeds if that raises the objective (hdg_refine_split,
-    hdg_refine_split_ladder)."""
+    hdg_refine_split_ladder);
+    --link-match: --Type untangle also reports how many hunks are in the right group under the
+    best one-to-one assignment of predicted to true groups (hdg_match): accuracy, purity, cover;
+    --link-score acc (needs --link-threshold refined): the ladder's rung is chosen by that
+    accuracy, pooled, every rung matched on the device."""
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument('--model', type=int, default=2, choices=(1, 2, 3, 4))
     p.add_argument('--loader', default='utils2', choices=('utils2', 'fast'))
     p.add_argument('--link-threshold', type=_threshold, default=0.5)
     p.add_argument('--link-rule', default='mean', choices=('mean', 'any', 'both'))
-    p.add_argument('--link-score', default='f1', choices=('f1', 'rand'))
+    p.add_argument('--link-score', default='f1', choices=('f1', 'rand', 'acc'))
     p.add_argument('--link-method', default='single', choices=('single', 'complete', 'average'))
     p.add_argument('--link-refine', type=int, default=0)
     p.add_argument('--link-ladder', type=_ladder, default=(0.05, 0.95, 19))
     p.add_argument('--link-merge', type=int, default=0)
     p.add_argument('--link-split', action='store_true')
+    p.add_argument('--link-match', action='store_true')
     a, rest = p.parse_known_args(argv)
+    if a.link_score == 'acc' and a.link_threshold != 'refined':
+        p.error("--link-score acc needs --link-threshold refined")
     if a.link_threshold == 'refined' and a.link_refine < 1:
         p.error("--link-threshold refined needs --link-refine N with N >= 1")
     if not 0 <= a.link_merge <= 16:
@@ -203,6 +215,8 @@ def main(argv=None, model_cls=None):
                                             score=extra.link_score, **how)[0]
             # without refinement the call is the one it always was
             more = {'refine': extra.link_refine} if extra.link_refine else {}
+            if extra.link_match:     # the matching accuracy, only when asked for
+                more['match'] = True
             model.untangle(args, threshold=threshold, rule=extra.link_rule, **how, **more,
                            **rounds)
         if args.Type == 'calibrate':  # not in the reference: the best link threshold, on the device

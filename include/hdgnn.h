@@ -778,6 +778,84 @@ int    hdg_refine_split_ladder(const hdg_shape* shape, const hdg_batch* batch,
                                void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * On-device matching (csrc/match.hip): how many hunks ended up in the right group.  Every
+ * decoder above is scored by pair counts; hdg_match scores sets of group ids, whatever made
+ * them, by the clustering accuracy under the best one-to-one assignment of predicted groups
+ * to true groups -- the assignment problem on the contingency table of the two partitions
+ * (hdgnn.metrics.match_counts restates the call, integer for integer).  Not a reference flow.
+ *
+ *   groups   [n_sets][batch][nc] i32, n_sets in [1, HDG_MT_MAX_SETS]: e.g. the rungs a ladder
+ *            call left on the device.  Predicted groups by hdg_refine's start rule: hunks
+ *            with the same id in [0, nc) are together, a hunk whose id is outside [0, nc) is
+ *            alone (no id is used as an index before it is range-checked).  The numbering
+ *            does not matter: any renumbering of a set gives the same mt row
+ *   true groups  hdg_untangle's: the components of y_pq | y_qp from batch->ybits, dense ids
+ *            ordered by smallest member; written to tgroups ([batch][nc]) when it is given
+ *   table    n_gt = the hunks in predicted group g and true group t.  Never built densely:
+ *            at most nc cells are non-zero.  Every sum below is at most nc <= 2048, all
+ *            arithmetic is integer, no result depends on an order of summation
+ *   mt       [n_sets][batch][HDG_MT_SLOTS] u64, every slot written by the call
+ *   HDG_MT_MATCHED  the optimum of the assignment problem on the table: the smaller side is
+ *            fully assigned, an empty cell counts 0.  The value is unique even where the
+ *            assignment is not.  accuracy = MATCHED / nc
+ *   mate     (optional) [n_sets][batch][nc] i32: per hunk the dense true-group id its predicted
+ *            group is assigned to, -1 if the group is unassigned or assigned through an
+ *            empty cell.  ONE optimal assignment: under ties it is not unique and not
+ *            canonical (the same bits on every run, but another implementation may return
+ *            another optimum).  What holds: it is constant on each predicted group,
+ *            injective over the groups where it is not -1, and
+ *            #{p : mate[p] == tgroups[p]} == MATCHED
+ *   workspace  hdg_match_workspace_bytes(shape, n_sets) bytes, 8-byte aligned: the true ids,
+ *            computed once for all sets; its content before the call does not matter
+ * Consequences: (A) max cell <= MATCHED <= min(PURITY, COVER) <= nc; (B) MATCHED == nc iff the
+ * two partitions are equal (SD = DS = 0 in hdg_untangle's row of the same groups), and then
+ * CELLS == ISOLATED == GROUPS == TGROUPS; (C) MATCHED >= the sum of the isolated cells.
+ * Two launches on `stream`.  k_mt_truth: one 1024-thread block per commit labels the true
+ * groups (ut_true_groups).  k_mt_match: grid (n_sets, batch), one 256-thread block per set and
+ * commit, all state in LDS: a predicted group is named by its smallest member; one walk over
+ * the nc hunks gives every hunk the size of its cell and whether it is the cell's first hunk;
+ * integer LDS atomics give row and column maxima and degrees; the isolated cells are taken
+ * as they are; on the residual graph (the other cells) the assignment is solved exactly by
+ * shortest augmenting paths with integer potentials, rows on the smaller residual side K',
+ * ties between equal slacks to the lowest column.
+ *   bounds   a component of the residual graph with c >= 2 cells has at most c + 1 rows and
+ *            columns together, so both sides together have at most 3 nc / 2 groups and
+ *            K' <= 3 nc / 4 (reached by components of two cells, rows and columns doubled in
+ *            turn); augmentations <= K'; a path takes at most K' + 1 columns, two barriers
+ *            each (the loops are capped at nc rows and nc + 1 steps); every scan of a step is
+ *            ceil(nc / 256) columns per thread; the cell walk is nc steps.  A potential is the
+ *            length of a shortest path of at most K' cells of weight <= nc: |potential| <=
+ *            nc K' < 2^22, far below the 2^30 that marks a column no path has reached
+ * No host synchronisation, no block waits for another, no float anywhere, no allocation:
+ * graph-capturable, the same bits on every run.  Only shape->batch, shape->nc and
+ * batch->ybits are read.  HDG_EINVAL (the message starts "hdg_match:"; nothing is launched)
+ * for batch outside [1, 65535], nc outside [2, 2048], n_sets outside [1, HDG_MT_MAX_SETS], a
+ * NULL groups, mt, batch, batch->ybits or workspace, or a workspace that is not 8-byte
+ * aligned.                                                                              */
+#define HDG_MT_SLOTS 8
+#define HDG_MT_GROUPS 0    /* predicted groups                                           */
+#define HDG_MT_TGROUPS 1   /* true groups                                                */
+#define HDG_MT_MATCHED 2   /* max over one-to-one assignments of predicted to true groups
+                              of the sum of n_gt over the assigned pairs: the hunks in the
+                              right group.  accuracy = MATCHED / nc                      */
+#define HDG_MT_PURITY 3    /* sum over predicted groups g of max_t n_gt                  */
+#define HDG_MT_COVER 4     /* sum over true groups t of max_g n_gt                       */
+#define HDG_MT_CELLS 5     /* cells with n_gt > 0                                        */
+#define HDG_MT_ISOLATED 6  /* cells that are the only non-zero cell of their row AND of
+                              their column (every optimum contains them); slot 7 is 0
+                              (non-zero only if a path of the solver found no column,
+                              which the bounds exclude: such a row's MATCHED is void)   */
+#define HDG_MT_MAX_SETS 64 /* = HDG_RL_MAX_RUNGS                                         */
+
+size_t hdg_match_workspace_bytes(const hdg_shape* shape, int32_t n_sets);  /* 0 on an error */
+int    hdg_match(const hdg_shape* shape, const hdg_batch* batch,
+                 const int32_t* groups  /* [n_sets][batch][nc] */, int32_t n_sets,
+                 int32_t* mate          /* [n_sets][batch][nc] or NULL */,
+                 int32_t* tgroups       /* [batch][nc] or NULL */,
+                 uint64_t* mt           /* [n_sets][batch][HDG_MT_SLOTS] */,
+                 void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Data parallelism over xGMI (one all-reduce of the flat gradient per step).
  *
  * Instead of an RCCL call between hdg_fwd_bwd and hdg_adam_tf, the step's reduction
