@@ -2308,30 +2308,12 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     if (wv >= SMAXC && wv < SMAXC + 8) x_item(8 + wv - SMAXC, lane);        // wave-uniform
   }
   __syncthreads();
-  uint32_t warm[2] = {0u, 0u};
   if constexpr (SPLIT) {
-    // dV1 and (DEFER) the parameter gradients deferred from M9 overlap the exchange
+    // dV1 and (DEFER) the parameter gradients deferred from M9 overlap the exchange.  (No
+    // L2 warm-up of the count matrices here: M11 reads the columns of the own node half,
+    // the ones M3 fetched.)
     pair_send(dnb, 2 * Nc, xout + 2 * XS, xtag(epoch, 3) ^ xsend, t);
     if (dnout) pair_send(dnc, 2 * Nc, xout + 2 * XS + Nc, xtag(epoch, 3) ^ xsend, t);
-    // waves 4-15 warm this XCD's L2 with the count matrices (M11 reads every column; M3
-    // fetched only the own half) while waves 0-3 run dV1.  DEFER: the loads are issued
-    // here and waited for only before the receive, after the deferred work (ks | kt are
-    // Nc Ne <= 80 x 256 words: at most two 64-byte lines per thread)
-    if (wv >= 4) {
-      const int nw = PL.ncst - PL.ks;                     // ks | kt words
-      if constexpr (DEFER) {
-        static_assert(2 * (NT_MID - 256) * 16 >= 16 * SMAXC * 256, "warm-up: two lines per thread");
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int w = (t - 256 + u * (NT_MID - 256)) * 16;
-          if (w < nw) warm[u] = pp[PL.ks + w];
-        }
-      } else {
-        uint32_t acc = 0;
-        for (int w = (t - 256) * 16; w < nw; w += (NT_MID - 256) * 16) acc ^= pp[PL.ks + w];
-        asm volatile("" ::"v"(acc));
-      }
-    }
   }
   // dV1 rows 0..7 and dc1: [n^T; 1] . Dalpha, n^T . Dbeta  (MFMA), tile w4 of 4
   auto dv1_tile = [=](const int w4, const int lane) {
@@ -2371,7 +2353,6 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     } else if (wv == NT_MID / 64 - 1) {
       dc2_row(lane);
     }
-    if constexpr (SPLIT) asm volatile("" ::"v"(warm[0]), "v"(warm[1]));
   } else {
     if (wv < 4) dv1_tile(wv, lane);
   }
@@ -2396,7 +2377,7 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
   MID_STAMP();
 
   // ---- M11: cross-graph backward: dx'_I = sum_c dn_c[0] ks[c][I] + dn_c[1] kt[c][I] ----
-  //   4 hunk ranges (one per group) -> partial rows in the dq slot of U
+  //   4 hunk ranges (one per group; split mode: 8) -> partial rows in the dq slot of U
   float* dxpart = U + 3 * NE4 * HS;
   // E2's neighbour x-lists (rows | columns, as staged for E1): back into LDS past the five
   // node slots of the E3 backward when they fit the words the hunk phases leave there (dead
@@ -2416,14 +2397,33 @@ __global__ __launch_bounds__(NT_MID) void k_commit_step(
     const uint16_t* kt = reinterpret_cast<const uint16_t*>(pp + PL.kt);
     // split mode: the own node half only, 8 hunk ranges x 128 nodes
     constexpr int NGX = SPLIT ? 8 : NG_MID, TX = NT_MID / NGX;
-    const int gx = t / TX, tx = t - gx * TX;
+    // a range is walked in chunks of CH hunks: the 2 CH count loads and the CH dn pairs of a
+    // chunk are all issued before its first product (one memory round trip per chunk, not
+    // one per hunk).  Hunks past the range's end read its last hunk and are dropped by
+    // select, so every load is unconditional; the two chains stay in ascending c.
+    constexpr int CH = 10;
+    static_assert(TX % 64 == 0, "M11: a hunk range is whole waves");
+    const int gx = __builtin_amdgcn_readfirstlane(t / TX), tx = t - gx * TX;
     const int cq = (Nc + NGX - 1) / NGX;
-    const int cb0 = gx * cq, cb1 = (cb0 + cq < Nc) ? cb0 + cq : Nc;
+    const int cb0 = gx * cq, cb1 = (cb0 + cq < Nc) ? cb0 + cq : Nc;   // empty when cb0 >= Nc
     for (int I = nlo + tx; I < nhi; I += TX) {
       float a0 = 0.f, a1 = 0.f;
-      for (int c = cb0; c < cb1; ++c) {
-        a0 = fmaf(dnb[2 * c], (float)ks[(size_t)c * Ne + I], a0);
-        a1 = fmaf(dnb[2 * c + 1], (float)kt[(size_t)c * Ne + I], a1);
+      for (int c0 = cb0; c0 < cb1; c0 += CH) {         // wave-uniform
+        uint16_t sv[CH], tv[CH];
+        float2 dv[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+          const int c = c0 + u < cb1 ? c0 + u : cb1 - 1;
+          sv[u] = ks[(size_t)c * Ne + I];
+          tv[u] = kt[(size_t)c * Ne + I];
+          dv[u] = *reinterpret_cast<const float2*>(dnb + 2 * c);
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+          const bool in = c0 + u < cb1;
+          a0 = in ? fmaf(dv[u].x, (float)sv[u], a0) : a0;
+          a1 = in ? fmaf(dv[u].y, (float)tv[u], a1) : a1;
+        }
       }
       dxpart[gx * NE4 + I] = a0 + a1;
     }
